@@ -7,14 +7,25 @@ vocab 10000, dropout 0.1, synthetic data (randn images, random caption ids), ran
 One step = encoder forward + projection + decoder forward + CE + backward + clip_grad_norm_(5.0)
 + AdamW, i.e. train.py:75-100 for one batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU, RCCL data parallel)
 
-Rank 0 prints ONE JSON line. `value` = pairs processed by all ranks / max-over-ranks wall time.
+Rank 0 prints ONE JSON line. `value` = pairs processed by all ranks / max-over-ranks wall time;
+`ms_per_step` = that wall time / K. A plain run does only this: set up, W warm-up steps, the K timed
+steps, one more step for `final_loss`, the line.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0), as float32 DIR/<name>.npy:
+loss, grad_norm (pre-clip total norm, clip coefficient), and master_weights / grads (the flat f32
+buffers after that step's AdamW; a fixed seeded sample of their elements when they are large). Weights,
+batch and dropout are seeded, so the same arguments give the same arrays on the same build.
+
+`--full` adds the measurements that take runs of their own:
 `roofline` = the dominant kernel's achieved algorithmic TFLOP/s (HIP events around each of its
 launches during an instrumented replay of the same steps) against the bf16 dense MFMA peak.
 `cpu_baseline` = the CPU oracle (oracle/ref_cpu.py, an fp32 PyTorch restatement of the reference
 path) timed on this host on a bounded sample (rank 0, N=1 only).
+`also` = the other single-GPU BASELINE configs (rank 0, N=1 only).
+--no-roofline / --no-cpu-baseline / --no-also drop one of them from a --full run.
 """
 from __future__ import annotations
 
@@ -440,6 +451,30 @@ def also_block(args):
     return out
 
 
+DUMP_SAMPLE = 4 << 20  # elements kept of a flat buffer larger than this (16 MiB as f32)
+
+
+def snapshot_outputs(loss, opt):
+    """What a caller of the step holds after it: the loss, the pre-clip gradient norm and clip coefficient,
+    and the flat f32 gradients and updated master weights. Device-side copies (the next step overwrites the
+    buffers in place); buffers above DUMP_SAMPLE elements are sampled at fixed seeded indices."""
+    st = opt.store
+    idx = None
+    if st.numel > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(20240)
+        idx = torch.randint(0, st.numel, (DUMP_SAMPLE,), generator=g).sort().values.to(st.master.device)
+    pick = (lambda t: t.index_select(0, idx)) if idx is not None else (lambda t: t.clone())
+    return {"loss": loss.detach().float().reshape(-1).clone(), "grad_norm": opt.norm_t.clone(),
+            "master_weights": pick(st.master), "grads": pick(st.grad)}
+
+
+def write_outputs(path, snap):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in snap.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def spawn_ranks(args) -> int:
     """--gpus N > 1 with no launcher (WORLD_SIZE unset): start N rank processes of this script, one per
     GPU, with the torchrun environment (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 /
@@ -485,8 +520,15 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--cpu-steps", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the `roofline` / `gemm_breakdown` blocks (instrumented "
+                         "eager steps), the `cpu_baseline` block and the `also` block (the other BASELINE configs). "
+                         "Default: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, gradient norm, gradients and updated master weights to "
+                         "DIR/<name>.npy (float32; large buffers as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the `cpu_baseline` block")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the `roofline` block")
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as ONE hipGraph (N=1). Default: eager launches, which let the backward's "
@@ -507,7 +549,8 @@ def main():
     ap.add_argument("--max-len", type=int, default=100, help="decode: ids per caption (config.MAX_SEQ_LEN)")
     ap.add_argument("--also-steps", type=int, default=10, help="timed configs[2] steps in the `also` block")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the `also` block (configs[2] train step and configs[4] decode in the same run, N=1)")
+                    help="--full without the `also` block (configs[2] / configs[3] train step and configs[4] decode in "
+                         "the same run, N=1)")
     ap.add_argument("--dp", action="store_true",
                     help="N=1 only: build DataParallel over a world-size-1 torch.distributed group (RCCL, backend "
                          "\"nccl\"; MIT_DIST_BACKEND=gloo to rehearse) so the step runs the N-GPU launch path -- count "
@@ -516,6 +559,8 @@ def main():
                          "(parallelism \"dp1-nccl\")")
     args = ap.parse_args()
     if args.workload == "decode":
+        if args.dump_outputs:
+            ap.error("--dump-outputs writes the train step's outputs (workloads train, clip336, cfg3)")
         return bench_decode(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -591,8 +636,9 @@ def main():
             return out_loss
     barrier()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     t_enq = time.perf_counter() - t0  # host time to enqueue the K steps (launches are asynchronous)
     barrier()
     elapsed = time.perf_counter() - t0
@@ -600,6 +646,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         elapsed = t.item()
+    # the last timed step's outputs, copied before the next step overwrites them in place
+    snap = snapshot_outputs(last, opt) if args.dump_outputs and rank == 0 and last is not None else None
     loss = step().item()
 
     pairs = args.batch * world * args.steps
@@ -624,7 +672,10 @@ def main():
                        ("hipGraph" if use_graph else "eager (Python per launch)"),
         "final_loss": round(loss, 4),
     }
-    if not args.no_roofline:
+    if snap is not None:
+        write_outputs(args.dump_outputs, snap)
+        del snap
+    if args.full and not args.no_roofline:
         import native
         probe = GemmProbe()
         native.set_gemm_probe(probe)
@@ -672,9 +723,9 @@ def main():
         out["gemm_breakdown"] = {names(k): {"tflops": round(v[1] / v[0] / 1e12, 1),
                                                         "ms_per_step": round(1e3 * v[0] * inplace[k][2] / v[2] / min(args.steps, 5), 3)}
                                  for k, v in agg.items()}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "train":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "train":
         out["cpu_baseline"] = cpu_baseline(model, args)
-    if rank == 0 and world == 1 and not args.no_also and args.workload == "train":
+    if args.full and rank == 0 and world == 1 and not args.no_also and args.workload == "train":
         out["also"] = also_block(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

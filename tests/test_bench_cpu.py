@@ -43,6 +43,39 @@ def test_workloads_name_known_encoders():
         assert label.startswith("configs["), name
 
 
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: a flat buffer above DUMP_SAMPLE elements is sampled at the same sorted indices every
+    time, smaller ones are written whole; every array is float32 and the files stay under 64 MB."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    from params import FlatParams
+    for rows, sampled in ((4500, True), (7, False)):
+        st = FlatParams([("a", (rows, 1000))], torch.device("cpu"), torch.float32)
+        st.master.copy_(torch.arange(st.numel, dtype=torch.float32))  # exact below 2^24: value = index
+        st.grad.copy_(-st.master)
+        opt = types.SimpleNamespace(store=st, norm_t=torch.tensor([2.0, 1.0]))
+        a = bench.snapshot_outputs(torch.tensor(3.5), opt)
+        st.master.zero_()  # the snapshot is a copy
+        b = bench.snapshot_outputs(torch.tensor(3.5), opt)
+        n = bench.DUMP_SAMPLE if sampled else st.numel
+        assert sampled == (st.numel > bench.DUMP_SAMPLE)
+        assert a["master_weights"].shape == a["grads"].shape == (n,)
+        assert torch.equal(a["grads"], b["grads"]) and torch.equal(a["grads"], -a["master_weights"])
+        assert (a["master_weights"][1:] >= a["master_weights"][:-1]).all() and not b["master_weights"].any()
+        out = tmp_path / f"dump{rows}"
+        bench.write_outputs(str(out), a)
+        files = sorted(os.listdir(out))
+        assert files == ["grad_norm.npy", "grads.npy", "loss.npy", "master_weights.npy"]
+        arrs = {f: np.load(out / f) for f in files}
+        assert all(v.dtype == np.float32 for v in arrs.values())
+        assert sum(v.nbytes for v in arrs.values()) <= 64e6
+        assert arrs["loss.npy"].tolist() == [3.5] and arrs["grad_norm.npy"].tolist() == [2.0, 1.0]
+
+
 @pytest.mark.parametrize("workload,survey,line", [
     ("train", 50.17, "r01_bench_run.json"),
     ("clip336", 406.37, "r01_bench_clip336_run.json"),

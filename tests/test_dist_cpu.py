@@ -78,7 +78,9 @@ def _worker(rank, world, port, q):
         loss = (loss_sum / count).detach().reshape(1)
         dp.finish_backward(loss)
         if rank == 0:
-            q.put((loss.item(), store.grad.clone(), store.names()))
+            # as a numpy array: pickled by value. A torch tensor travels as a file descriptor that the parent
+            # fetches from this process, which may already have exited by then
+            q.put((loss.item(), store.grad.clone().numpy(), store.names()))
     finally:
         dist.destroy_process_group()
 
@@ -92,6 +94,7 @@ def test_dp2_gloo_matches_single_process_reference():
     for p in procs:
         p.start()
     loss, grad, names = q.get(timeout=300)
+    grad = torch.from_numpy(grad)
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0

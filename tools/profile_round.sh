@@ -1,5 +1,6 @@
 #!/bin/bash
-# rocprofv3 evidence for bench.py (run on the GPU box from the repo root; outputs to gpurun_out/):
+# rocprofv3 evidence for bench.py (run on the GPU box from the repo root; outputs under $OUT_ROOT, default
+# bench_out/):
 #   1) kernel trace + stats of the default bench command (native replay, encoder prefetch stream,
 #      weight-gradient side stream) -> trace   [timeline: tools/timeline.py]
 #   2) the same with --no-prefetch (encoder inline: per-kernel attribution without overlap)
@@ -11,23 +12,24 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 TAG=${1:-r04}
-OUT=gpurun_out/prof_$TAG
+OUT_ROOT=${OUT_ROOT:-bench_out}
+OUT=$OUT_ROOT/prof_$TAG
 mkdir -p $OUT
 # WORKLOAD=clip336 / cfg3: the same passes over that workload (bench.py --workload)
 ARGS="--no-cpu-baseline --no-also --steps 10 --warmup 3${WORKLOAD:+ --workload $WORKLOAD}"
 P="rocprofv3 --output-format rocpd csv"
-timeout -k 10 300 $P --kernel-trace --stats -d $OUT/trace -o run -- python3 bench.py $ARGS > $OUT/trace.json 2> $OUT/trace.err &&
+timeout -k 10 300 $P --kernel-trace --stats -d $OUT/trace -o run -- python3 bench.py --full $ARGS > $OUT/trace.json 2> $OUT/trace.err &&
 timeout -k 10 300 $P --kernel-trace --stats -d $OUT/trace_noprefetch -o run -- python3 bench.py $ARGS --no-prefetch --no-roofline > $OUT/trace_noprefetch.json 2> $OUT/trace_noprefetch.err &&
 timeout -k 10 300 $P --pmc FETCH_SIZE --kernel-trace -d $OUT/fetch -o run -- python3 bench.py $ARGS --no-roofline > $OUT/fetch.json 2> $OUT/fetch.err &&
 timeout -k 10 300 $P --pmc WRITE_SIZE --kernel-trace -d $OUT/write -o run -- python3 bench.py $ARGS --no-roofline > $OUT/write.json 2> $OUT/write.err &&
 timeout -s KILL 300 $P --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $OUT/sq -o run -- python3 bench.py $ARGS --no-roofline > $OUT/sq.json 2> $OUT/sq.err
-# condense on the box (the rocpd databases exceed gpurun_out's copy-back cap): summaries under
+# condense on the box (the rocpd databases are too large to copy back): summaries under
 # $OUT/keep, databases deleted
 f() { find $OUT/$1 -name "$2" | head -n 1; }
 mkdir -p $OUT/keep &&
 python3 tools/rocpd_summary.py --trace $(f trace '*results.db') --fetch $(f fetch '*results.db') \
-  --write $(f write '*results.db') --sq $(f sq '*results.db') --trace-csv $(f trace '*kernel_trace.csv') --bench-json $OUT/trace.json $( [ -f gpurun_out/bench_$TAG.json ] && echo --bench-plain gpurun_out/bench_$TAG.json ) \
-  --command "rocprofv3 --kernel-trace --stats / --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -- python3 bench.py $ARGS" \
+  --write $(f write '*results.db') --sq $(f sq '*results.db') --trace-csv $(f trace '*kernel_trace.csv') --bench-json $OUT/trace.json $( [ -f $OUT_ROOT/bench_$TAG.json ] && echo --bench-plain $OUT_ROOT/bench_$TAG.json ) \
+  --command "rocprofv3 --kernel-trace --stats / --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -- python3 bench.py --full $ARGS" \
   --out $OUT/keep/$TAG > $OUT/keep/summary.txt &&
 cp $(f trace '*kernel_stats.csv') $OUT/keep/${TAG}_bench_kernel_stats.csv &&
 cp $(f trace_noprefetch '*kernel_stats.csv') $OUT/keep/${TAG}_bench_noprefetch_kernel_stats.csv &&
