@@ -56,13 +56,13 @@ struct Epi {
   float dscale;
   int dropout;
   int vec;  // 16-B vector epilogue legal (alignments / leading dims / N multiple of 8)
-  // LayerNorm folded into the GEMM (256 kernel, STG 3): A = the raw rows x, the epilogue applies
+  // LayerNorm folded into the GEMM (256 kernel, STG_LN_FOLD): A = the raw rows x, the epilogue applies
   // rstd_m (acc - mean_m colsum_n) + bias_n with (mean, rstd) merged from ln_stats [M][ln_parts][2]
   const float* ln_stats;
   const float* ln_colsum;
   int ln_parts;
   float ln_eps;
-  // per-64-column (mean, M2) of each output row (256 kernel, STG 4): stats_out [M][N / 64][2]
+  // per-64-column (mean, M2) of each output row (256 kernel, STG_ROW_STATS): stats_out [M][N / 64][2]
   float* stats_out;
   // the greedy argmax of each row folded in (128 kernel, gathered epilogue): keys [MIT_ARGMAX_SLOTS][M]
   unsigned long long* argmax_keys;
@@ -78,6 +78,17 @@ __device__ __forceinline__ uint64_t argmax_key(float v, long col) {
 
 constexpr int ACT_RT = -1;
   // activation read from Epi::act at run time (generic instance)
+
+// Epilogue stage of the 256 kernels (template argument STG; plain ints, not an enum, so the kernels'
+// mangled names do not depend on it). A template flag, not a run-time branch: two epilogues in one
+// instance spill in the K loop. Which (layout, activation, dropout, stage) instances exist: has_256 /
+// has_256w below; which one a launch gets: plan_gemm.
+constexpr int STG_REG = 0;         // f32 outputs and non-gatherable epilogues: from registers (K-contig A, reg_epilogue) or
+                                   // through the fp32 LDS stage (MN-contig A, per-segment operands)
+constexpr int STG_STAGED = 1;      // bf16 out, gatherable, K-contig A: each wave's LDS stage (stage_epilogue), no operand
+constexpr int STG_STAGED_OPS = 2;  // ... with the residual / aux block
+constexpr int STG_LN_FOLD = 3;     // ... LayerNorm-folded A (Epi::ln_stats), no operand
+constexpr int STG_ROW_STATS = 4;   // ... residual + the output rows' per-64-column statistics (Epi::stats_out)
 
 // FAST: bf16 vector epilogues use the one-exp GELU (gelu_fast, relative error <= 6.6e-6, far below
 // bf16 rounding); the scalar / fp32-parity path keeps ocml's erff
@@ -887,11 +898,8 @@ __device__ __forceinline__ void stage_epilogue(const f32x4 (&acc)[8][4], const E
   }
 }
 
-// STG (bf16 out, gathered epilogue, K-contig A): 1 = the LDS-staged epilogue without operands, 2 = with
-// the residual / aux block, 3 = LayerNorm-folded A (no operand), 4 = residual + the output rows'
-// per-64-column statistics; 0 = the register (f32 out) or LDS-stage (MN-contig A) epilogue. A template
-// flag, not a run-time branch: two epilogues in one instance spill in the K loop.
-template <int ALAY, int BLAY, int ACT, bool DROP, int STG = 0>
+// STG: the epilogue stage (STG_* above)
+template <int ALAY, int BLAY, int ACT, bool DROP, int STG = STG_REG>
 __global__ __launch_bounds__(512) void gemm256_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B, void* C,
                                                       long M, long N, long K, long lda, long ldb, long ldc, int a_bytes,
                                                       int b_bytes, Epi e, float* __restrict__ ws,
@@ -932,7 +940,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const bf16* __restrict__ A
   // is gatherable, else the C^T blocks are staged through LDS transposed
   constexpr bool REG = ALAY == MIT_K_CONTIG;
   const bool regepi = REG && epi_gatherable(e);
-  const bool stage = STG && regepi;  // LDS-staged bf16 epilogue (stage_epilogue)
+  const bool stage = STG != STG_REG && regepi;  // LDS-staged bf16 epilogue (stage_epilogue)
   float rs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
   const int nk = (int)((ke - kb + BK - 1) / BK);
@@ -991,7 +999,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const bf16* __restrict__ A
                     : __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][kk], bf[j][kk], acc[ih * IH0 + i][jh * 2 + j], 0, 0, 0);
   };
 
-  // LN fold (STG 3): each of the tile's 256 rows' K / 64 statistics partials merged ONCE here (thread r
+  // LN fold (STG_LN_FOLD): each of the tile's 256 rows' K / 64 statistics partials merged ONCE here (thread r
   // takes row m0 + r, Chan's rule in column order) into (rstd, -rstd mean) in LDS past the K-tile buffers,
   // read by the epilogue's 8 rows per lane. The partial loads go out before the first LDS-DMA, so the
   // K loop's counted vmcnt waits (younger DMAs only) stay exact, and the merge after the prologue's DMA
@@ -1000,15 +1008,15 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const bf16* __restrict__ A
   // staged epilogues: the tile's 256 bias values (and LN-fold column sums) loaded here too, into LDS
   float* lcol = (float*)(smem + SMEM2_BYTES + 2048);
   float pbias = 0.f, pcols = 0.f;
-  if constexpr (STG != 0) {
+  if constexpr (STG != STG_REG) {
     const long c = n0 + tid;
     if (tid < B2 && c < N) {
       if (e.bias) pbias = e.bias[c];
-      if constexpr (STG == 3) pcols = e.ln_colsum[c];
+      if constexpr (STG == STG_LN_FOLD) pcols = e.ln_colsum[c];
     }
   }
-  f32x2 lnp[STG == 3 ? LN_PMAX : 1];
-  if constexpr (STG == 3) {
+  f32x2 lnp[STG == STG_LN_FOLD ? LN_PMAX : 1];
+  if constexpr (STG == STG_LN_FOLD) {
     const long row = m0 + tid;
     const bool ok = tid < BMT && row < M;
 #pragma unroll
@@ -1021,7 +1029,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const bf16* __restrict__ A
   issue(1, 0, 0);
   issue(1, 1, 0);
   const bool b01 = issue(1, 0, 1);
-  if constexpr (STG == 3) {
+  if constexpr (STG == STG_LN_FOLD) {
     if (tid < BMT) {  // Chan, partial p (64 columns) onto the first 64 p: weights 1 / (p + 1) are constants
       float mu = 0.f, q = 0.f;
 #pragma unroll
@@ -1035,10 +1043,10 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const bf16* __restrict__ A
       ln_rows[tid] = f32x2{rs, -rs * mu};
     }
   }
-  if constexpr (STG != 0) {
+  if constexpr (STG != STG_REG) {
     if (tid < B2) {
       lcol[tid] = pbias;
-      if constexpr (STG == 3) lcol[256 + tid] = pcols;
+      if constexpr (STG == STG_LN_FOLD) lcol[256 + tid] = pcols;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // visible to every wave past the next barrier
   }
@@ -1102,13 +1110,14 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const bf16* __restrict__ A
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (regepi) {
-    if constexpr (STG) {
+    if constexpr (STG != STG_REG) {
       if (stage) {
         // group 0 stages into the buffer NOT holding the last K-tile (its last reads were >= 2 phases
         // ago), group 1 into the last K-tile's buffer (every read of it returned by the last barrier)
         const int buf = wr == 0 ? (nk & 1) : ((nk - 1) & 1);
         char* stg = smem + buf * BUF_BYTES + wc * 16384;
-        stage_epilogue<ACT, DROP, STG == 2 || STG == 4, STG == 3 ? 1 : (STG == 4 ? 2 : 0)>(
+        stage_epilogue<ACT, DROP, STG == STG_STAGED_OPS || STG == STG_ROW_STATS,
+                       STG == STG_LN_FOLD ? 1 : (STG == STG_ROW_STATS ? 2 : 0)>(
             acc, e, C, ldc, M, N, m0 + wr * HR, n0 + wc * 64, lane, stg, lcol + wc * 64, ln_rows + wr * HR);
         return;
       }
@@ -1186,8 +1195,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const bf16* __restrict__ A
 }
 
 // ------------------------------------------------------------------------------------------------
-// 256x256 tile with ONE wave per SIMD (opt-in: mit_gemm_set_variant(4); NT, bf16, K % 64 == 0, the STG 1 /
-// 3 / 4 epilogues): 4 waves as 2 (M) x 2 (N), each owning a 128x128 output tile = 8 x 8 accumulator blocks
+// 256x256 tile with ONE wave per SIMD (opt-in: mit_gemm_set_variant(4); NT, bf16, K % 64 == 0, the STG_STAGED /
+// STG_LN_FOLD / STG_ROW_STATS epilogues): 4 waves as 2 (M) x 2 (N), each owning a 128x128 output tile = 8 x 8 accumulator blocks
 // (256 registers per lane, AGPRs, accumulated in place by inline-asm MFMAs). The K-tile's LDS image and DMA
 // plan are gemm256_kernel's (each wave issues the pieces of two of its virtual waves; the K-tile step in
 // soffset). Per K-tile two phases of 64 MFMAs, one barrier:
@@ -1307,11 +1316,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const long c = n0 + tid;
     if (c < N) {
       if (e.bias) pbias = e.bias[c];
-      if constexpr (STG == 3) pcols = e.ln_colsum[c];
+      if constexpr (STG == STG_LN_FOLD) pcols = e.ln_colsum[c];
     }
   }
-  f32x2 lnp[STG == 3 ? LN_PMAX : 1];
-  if constexpr (STG == 3) {
+  f32x2 lnp[STG == STG_LN_FOLD ? LN_PMAX : 1];
+  if constexpr (STG == STG_LN_FOLD) {
     const long row = m0 + tid;
     const bool ok = row < M;
 #pragma unroll
@@ -1320,7 +1329,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
   issue_tile(0);
   issue_tile(1);
-  if constexpr (STG == 3) {
+  if constexpr (STG == STG_LN_FOLD) {
     float mu = 0.f, q = 0.f;
 #pragma unroll
     for (int p = 0; p < LN_PMAX; ++p)
@@ -1333,7 +1342,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     ln_rows[tid] = f32x2{rs, -rs * mu};
   }
   lcol[tid] = pbias;
-  if constexpr (STG == 3) lcol[256 + tid] = pcols;
+  if constexpr (STG == STG_LN_FOLD) lcol[256 + tid] = pcols;
   asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
   bar_raw();
 #pragma unroll
@@ -1359,7 +1368,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) a2[i][j] = acc[i][h * 4 + j];
-    stage_epilogue<ACT, false, STG == 4, STG == 3 ? 1 : (STG == 4 ? 2 : 0)>(
+    stage_epilogue<ACT, false, STG == STG_ROW_STATS, STG == STG_LN_FOLD ? 1 : (STG == STG_ROW_STATS ? 2 : 0)>(
         a2, e, C, ldc, M, N, m0 + wr * 128, n0 + wc * 128 + h * 64, lane, stg, lcol + wc * 128 + h * 64, ln_rows + wr * 128);
   }
 }
@@ -1537,14 +1546,13 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_grouped(GroupArgs ga) 
 
 // split-K plan for a plain-epilogue bf16 GEMM: only when the output has too few 128x128 tiles to
 // fill 256 CUs and K is long (the weight-gradient shapes). Returns 1 (no split) otherwise.
-int splitk_plan(long M, long N, long K, long* kchunk, int a_layout = MIT_MN_CONTIG) {
+int splitk_plan(long M, long N, long K, long* kchunk) {
   const long tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   *kchunk = K;
   if (tiles >= 256 || K < 1024 || N % 8) return 1;
   // blocks the split aims for: 256 for the data gradients (dX fc_out, K = 10000 on 128 tiles: +0.4 % step
   // over 128) and the weight gradients (128 / 256 / 384 within +-0.3 % in the step)
   const long target = 256;
-  (void)a_layout;
   long s = (target + tiles - 1) / tiles;
   s = min(s, K / 512);
   s = min(s, 16L);
@@ -1622,19 +1630,22 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------------------
 // host side: kernel / epilogue-instance selection
 // ------------------------------------------------------------------------------------------------
+//   make_epi      the epilogue facts of the args (the planner and the kernels see the same vec / gatherable)
+//   plan_gemm     THE kernel choice: family, {act, dropout} instance, 256-kernel stage, split-K
+//   has_*         which template instances are compiled (consulted by plan_gemm and launch_gemm)
+//   launch_gemm   the plan -> one launch_<family><instance>()
+// mit_gemm = validate, plan, launch; mit_gemm_plan = plan, reported as a tile edge.
 
+// every instance's dynamic-LDS size is registered once, by the initialiser of a function-local static
+// (thread-safe) in front of its first launch. The plan is a function of the args alone, so the warm-up
+// launches in front of a graph capture run -- and register -- exactly the instances the capture runs.
 template <typename KernelT>
-void set_lds(KernelT k, int bytes) {
+bool set_lds(KernelT k, int bytes) {
   (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  return true;
 }
 
-// split-K decision for a bf16 GEMM on the 128x128 kernel. The workspace's first WS_HDR bytes hold
-// the in-launch combine's per-tile counters; slabs follow.
-constexpr long WS_HDR = 4096;
-struct Split {
-  int ks = 1;
-  long kchunk = 0;
-};
+inline bool al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 
 int g_num_cus = 0;
 int num_cus() {
@@ -1646,327 +1657,15 @@ int num_cus() {
   return g_num_cus;
 }
 
-// 8 waves per 128x128 block (2 per SIMD, each issuing half the LDS-DMA pieces of a K-tile): with 4
-// waves every K-tile's 8 DMA pieces per wave sat serially in front of its 32 MFMAs (+2.7 % step)
-template <int AL, int BL, int ACT, bool DROP>
-void launch_bf16(const mit_gemm_args* g, const Epi& e, int a_bytes, int b_bytes, const Split& sp, hipStream_t s) {
-  const int ksplit = sp.ks;
-  const long kchunk = sp.ks > 1 ? sp.kchunk : g->K;
-  float* ws = g->workspace ? (float*)((char*)g->workspace + WS_HDR) : nullptr;
-  const long nbm = (g->M + BM - 1) / BM, nbn = (g->N + BN - 1) / BN;
-  const long nblk = nbm * nbn * ksplit;
-  static bool attr = false;
-  if (!attr) {
-    set_lds(gemm_bf16_kernel<AL, BL, ACT, DROP>, smem_bytes(2));
-    attr = true;
-  }
-  hipLaunchKernelGGL((gemm_bf16_kernel<AL, BL, ACT, DROP>), dim3((unsigned)nblk), dim3(512), smem_bytes(2), s,
-                     (const bf16*)g->A, (const bf16*)g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes,
-                     b_bytes, e, ksplit, kchunk, ws, g->rowsum);
-}
-
-template <int ACT, bool DROP>
-void launch_rs(const mit_gemm_args* g, const Epi& e, int a_bytes, int b_bytes, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    set_lds(gemm_rs_kernel<ACT, DROP>, RS_SMEM);
-    attr = true;
-  }
-  const long nb = ((g->M + 63) / 64) * ((g->N + 63) / 64);
-  hipLaunchKernelGGL((gemm_rs_kernel<ACT, DROP>), dim3((unsigned)nb), dim3(256), RS_SMEM, s, (const bf16*)g->A,
-                     (const bf16*)g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes, b_bytes, e);
-}
-
-// 0 = pick per shape, 1 = always the 128x128 kernel, 2 = the 256x256 kernel wherever it has an
-// instance for the epilogue, 3 = the register-streaming kernel where it applies (tests / tools)
+// mit_gemm_set_variant: 0 = pick per shape, 1 = always the 128x128 kernel, 2 = the 256x256 kernel wherever
+// it has an instance for the epilogue, 3 = the register-streaming kernel where it applies, 4 = as 0 with
+// the one-wave-per-SIMD 256 kernel where it applies (tests / tools)
 #ifndef MIT_GEMM_DEFAULT_VARIANT
 #define MIT_GEMM_DEFAULT_VARIANT 0  // A/B builds (tools/build_variants.sh) may start in another variant
 #endif
 int g_variant = MIT_GEMM_DEFAULT_VARIANT;
-int gemm_variant() { return g_variant; }
 
-// bf16 outputs with a gatherable epilogue leave through each wave's LDS stage (STG 1: no operand,
-// STG 2: with the residual / aux block); f32 outputs and the other epilogues through registers
-template <int AL, int BL, int ACT, bool DROP>
-void launch_bf16_256(const mit_gemm_args* g, const Epi& e, int a_bytes, int b_bytes, hipStream_t s) {
-  const long nbm = (g->M + 255) / 256, nbn = (g->N + B2 - 1) / B2;
-  static bool attr = false;
-  if (!attr) {
-    set_lds(gemm256_kernel<AL, BL, ACT, DROP>, SMEM2_BYTES);
-    if constexpr (AL == MIT_K_CONTIG) {
-      set_lds(gemm256_kernel<AL, BL, ACT, DROP, 1>, SMEM2_EPI_BYTES);
-      if constexpr (ACT == MIT_ACT_NONE) set_lds(gemm256_kernel<AL, BL, ACT, DROP, 2>, SMEM2_EPI_BYTES);
-    }
-    if constexpr (AL == MIT_K_CONTIG && BL == MIT_K_CONTIG) {
-      if constexpr (ACT == MIT_ACT_NONE) set_lds(gemm256_kernel<AL, BL, ACT, DROP, 4>, SMEM2_EPI_BYTES);
-      if constexpr (!DROP) set_lds(gemm256_kernel<AL, BL, ACT, DROP, 3>, SMEM2_EPI_BYTES);
-    }
-    attr = true;
-  }
-  const dim3 grid((unsigned)(nbm * nbn));
-  if constexpr (AL == MIT_K_CONTIG && BL == MIT_K_CONTIG && !DROP) {  // one-wave-per-SIMD prototype (variant 4)
-    if (gemm_variant() == 4 && g->K % BK == 0 && (!e.res || e.stats_out) && !e.aux && !e.out_f32 && epi_gatherable(e)) {
-      static bool wattr = false;
-      if (!wattr) {
-        set_lds(gemm256w_kernel<ACT, 1>, SMEM2_EPI_BYTES);
-        set_lds(gemm256w_kernel<ACT, 3>, SMEM2_EPI_BYTES);
-        if constexpr (ACT == MIT_ACT_NONE) set_lds(gemm256w_kernel<ACT, 4>, SMEM2_EPI_BYTES);
-        wattr = true;
-      }
-      if constexpr (ACT == MIT_ACT_NONE) {
-        if (e.stats_out) {
-          hipLaunchKernelGGL((gemm256w_kernel<ACT, 4>), grid, dim3(256), SMEM2_EPI_BYTES, s, (const bf16*)g->A,
-                             (const bf16*)g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes, b_bytes, e);
-          return;
-        }
-      }
-      if (e.ln_stats)
-        hipLaunchKernelGGL((gemm256w_kernel<ACT, 3>), grid, dim3(256), SMEM2_EPI_BYTES, s, (const bf16*)g->A,
-                           (const bf16*)g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes, b_bytes, e);
-      else
-        hipLaunchKernelGGL((gemm256w_kernel<ACT, 1>), grid, dim3(256), SMEM2_EPI_BYTES, s, (const bf16*)g->A,
-                           (const bf16*)g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes, b_bytes, e);
-      return;
-    }
-  }
-  if constexpr (AL == MIT_K_CONTIG && BL == MIT_K_CONTIG) {  // LayerNorm fold / statistics (mit_gemm checked them)
-    if constexpr (!DROP) {
-      if (e.ln_stats) {
-        hipLaunchKernelGGL((gemm256_kernel<AL, BL, ACT, DROP, 3>), grid, dim3(512), SMEM2_EPI_BYTES, s, (const bf16*)g->A,
-                           (const bf16*)g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes, b_bytes, e,
-                           (float*)g->workspace, g->rowsum);
-        return;
-      }
-    }
-    if constexpr (ACT == MIT_ACT_NONE) {
-      if (e.stats_out) {
-        hipLaunchKernelGGL((gemm256_kernel<AL, BL, ACT, DROP, 4>), grid, dim3(512), SMEM2_EPI_BYTES, s, (const bf16*)g->A,
-                           (const bf16*)g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes, b_bytes, e,
-                           (float*)g->workspace, g->rowsum);
-        return;
-      }
-    }
-  }
-  if constexpr (AL == MIT_K_CONTIG) {
-    const bool ops = e.res || e.aux;
-    if (epi_gatherable(e) && !e.out_f32) {
-      if constexpr (ACT == MIT_ACT_NONE) {
-        if (ops) {
-          hipLaunchKernelGGL((gemm256_kernel<AL, BL, ACT, DROP, 2>), grid, dim3(512), SMEM2_EPI_BYTES, s, (const bf16*)g->A,
-                             (const bf16*)g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes, b_bytes, e,
-                             (float*)g->workspace, g->rowsum);
-          return;
-        }
-      }
-      if (!ops) {
-        hipLaunchKernelGGL((gemm256_kernel<AL, BL, ACT, DROP, 1>), grid, dim3(512), SMEM2_EPI_BYTES, s, (const bf16*)g->A,
-                           (const bf16*)g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes, b_bytes, e,
-                           (float*)g->workspace, g->rowsum);
-        return;
-      }
-    }
-  }
-  hipLaunchKernelGGL((gemm256_kernel<AL, BL, ACT, DROP>), grid, dim3(512), SMEM2_BYTES, s, (const bf16*)g->A,
-                     (const bf16*)g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes, b_bytes, e,
-                     (float*)g->workspace, g->rowsum);
-}
-
-// register-streaming kernel (gemm_rs_kernel): the decode step's B-row GEMMs (M <= 256) with a short
-// K and N <= 2048 -- 7.2 vs 9.9 us per launch on 256 x {512, 1536, 2048} x 512. Everywhere else it
-// loses: each wave streams its own A and B fragments from L2 (8 FLOP per L2 byte vs 64 for the 128
-// kernel's LDS tiles): 2.5-3x slower on the M = 4032 decoder shapes, 2x on the decode fc_out
-// (tools/blas_reference.py)
-bool use_rs(const mit_gemm_args* g) {
-  if (g->a_layout != MIT_K_CONTIG || g->b_layout != MIT_K_CONTIG || g->rowsum || g->ln_stats || g->stats_out) return false;
-  const int v = gemm_variant();
-  if (v == 3) return true;
-  if (v != 0 && v != 4) return false;
-  return g->M <= 256 && g->N <= 2048 && g->K <= 1024;
-}
-
-// Occupancy-quantised cost model: the 128x128 kernel runs 2 blocks per CU, the 256x256 kernel 1;
-// a "round" fills every slot once, and a round of the 256 kernel moves 4 tiles' worth of 128x128
-// work per CU-slot at REL256 x the 128 kernel's per-FLOP speed (tools/gemm_bench.py).
-bool use_256(long M, long N, long K, int a_layout, int tiles) {
-  const int v = gemm_variant();
-  if (v == 1) return false;
-  if (v == 2) return true;
-  // the MN-contig-A instances (weight gradients) exceed 256 VGPRs and spill: 128 kernel (+ split-K)
-  if (a_layout != MIT_K_CONTIG) return false;
-  if (M < 256 || N < 256 || K < 128 || tiles == 128) return false;
-  if (tiles == 256) return true;  // the caller runs other work beside this launch (mit_gemm_args.tiles)
-  const double REL256 = 1.3, CUS = 256.0;
-  const double t128 = (double)(((M + 127) / 128) * ((N + 127) / 128));
-  const double t256 = (double)(((M + 255) / 256) * ((N + 255) / 256));
-  const double c128 = std::ceil(t128 / (2 * CUS));             // rounds of 2 concurrent 128-tiles per CU
-  const double c256 = std::ceil(t256 / CUS) * 2.0 / REL256;    // one 256-tile = 4 128-tiles on 1 slot of 2
-  return c256 < c128;
-}
-
-// epilogue instance for a bf16 GEMM: {act, dropout} as template parameters where an instance
-// exists (the combinations the train step uses), else the generic run-time instance
-enum EpiKind { EK_PLAIN, EK_RELU, EK_RELU_DROP, EK_GELU, EK_QGELU, EK_GENERIC };
-EpiKind epi_kind(const mit_gemm_args* g) {
-  const bool drop = g->drop_p > 0.f;
-  if (g->act == MIT_ACT_NONE && !drop) return EK_PLAIN;
-  if (g->a_layout != MIT_K_CONTIG || g->b_layout != MIT_K_CONTIG) return EK_GENERIC;
-  if (g->act == MIT_ACT_RELU) return drop ? EK_RELU_DROP : EK_RELU;
-  if (drop) return EK_GENERIC;
-  return g->act == MIT_ACT_GELU ? EK_GELU : EK_QGELU;
-}
-
-template <int AL, int BL>
-void launch_layout(const mit_gemm_args* g, const Epi& e, int ab, int bb, const Split& sp, bool big, hipStream_t s) {
-  const EpiKind k = epi_kind(g);
-  if constexpr (AL == MIT_K_CONTIG && BL == MIT_K_CONTIG) {
-    if (sp.ks == 1 && use_rs(g)) {
-      switch (k) {
-        case EK_PLAIN: return launch_rs<MIT_ACT_NONE, false>(g, e, ab, bb, s);
-        case EK_RELU: return launch_rs<MIT_ACT_RELU, false>(g, e, ab, bb, s);
-        case EK_RELU_DROP: return launch_rs<MIT_ACT_RELU, true>(g, e, ab, bb, s);
-        case EK_GELU: return launch_rs<MIT_ACT_GELU, false>(g, e, ab, bb, s);
-        case EK_QGELU: return launch_rs<MIT_ACT_QUICK_GELU, false>(g, e, ab, bb, s);
-        default: return launch_rs<ACT_RT, true>(g, e, ab, bb, s);
-      }
-    }
-  }
-  // the 256 kernel's activation instances take no residual / aux operand (gemm256_kernel, XOPS)
-  if (big && k != EK_GENERIC && (g->act == MIT_ACT_NONE || (!g->residual && !g->aux))) {
-    if constexpr (AL == MIT_K_CONTIG && BL == MIT_K_CONTIG) {
-      switch (k) {
-        case EK_RELU: return launch_bf16_256<AL, BL, MIT_ACT_RELU, false>(g, e, ab, bb, s);
-        case EK_RELU_DROP: return launch_bf16_256<AL, BL, MIT_ACT_RELU, true>(g, e, ab, bb, s);
-        case EK_GELU: return launch_bf16_256<AL, BL, MIT_ACT_GELU, false>(g, e, ab, bb, s);
-        case EK_QGELU: return launch_bf16_256<AL, BL, MIT_ACT_QUICK_GELU, false>(g, e, ab, bb, s);
-        default: break;
-      }
-    }
-    return launch_bf16_256<AL, BL, MIT_ACT_NONE, false>(g, e, ab, bb, s);
-  }
-  if constexpr (AL == MIT_K_CONTIG && BL == MIT_K_CONTIG) {
-    switch (k) {
-      case EK_PLAIN: return launch_bf16<AL, BL, MIT_ACT_NONE, false>(g, e, ab, bb, sp, s);
-      case EK_RELU: return launch_bf16<AL, BL, MIT_ACT_RELU, false>(g, e, ab, bb, sp, s);
-      case EK_RELU_DROP: return launch_bf16<AL, BL, MIT_ACT_RELU, true>(g, e, ab, bb, sp, s);
-      case EK_GELU: return launch_bf16<AL, BL, MIT_ACT_GELU, false>(g, e, ab, bb, sp, s);
-      case EK_QGELU: return launch_bf16<AL, BL, MIT_ACT_QUICK_GELU, false>(g, e, ab, bb, sp, s);
-      default: return launch_bf16<AL, BL, ACT_RT, true>(g, e, ab, bb, sp, s);
-    }
-  }
-  if (k == EK_PLAIN) return launch_bf16<AL, BL, MIT_ACT_NONE, false>(g, e, ab, bb, sp, s);
-  return launch_bf16<AL, BL, ACT_RT, true>(g, e, ab, bb, sp, s);
-}
-
-template <int AL, int BL>
-void launch_f32(const mit_gemm_args* g, const Epi& e, hipStream_t s) {
-  dim3 grid((unsigned)((g->N + 63) / 64), (unsigned)((g->M + 63) / 64));
-  hipLaunchKernelGGL((gemm_f32_kernel<AL, BL>), grid, dim3(256), 0, s, (const float*)g->A, (const float*)g->B, g->C, g->M,
-                     g->N, g->K, g->lda, g->ldb, g->ldc, e, g->rowsum);
-}
-
-inline bool al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
-Split plan_split(const mit_gemm_args* g) {
-  Split p;
-  p.kchunk = g->K;
-  if (!g->workspace || !al16(g->workspace)) return p;
-  // plain epilogues only: splitting the decoder's long-K GEMMs that carry a bias / residual (fc2 forward,
-  // the fc1 / self_in data gradients; the reduce applying them) cost 1.8 % of the step (12639 / 12702 vs
-  // 12885 / 12898 pairs/s): their extra workgroups and reduce launches take CUs from the encoder prefetch
-  const bool plain = !g->bias && g->act == MIT_ACT_NONE && !g->residual && !g->aux && g->drop_p <= 0.f;
-  long kc;
-  if (plain && g->ldc % 4 == 0 && al16(g->C)) {
-    const int s = splitk_plan(g->M, g->N, g->K, &kc, g->a_layout);
-    if (s > 1 && splitk_ws_bytes(g->M, g->N, s) <= g->workspace_bytes) {
-      p.ks = s;
-      p.kchunk = kc;
-      return p;
-    }
-  }
-  return p;
-}
-
-}  // namespace
-
-extern "C" int mit_gemm_set_variant(int v) {
-  MIT_CHECK_ARG(v >= 0 && v <= 4, "mit_gemm_set_variant: %d not in {0,1,2,3,4}", v);
-  g_variant = v;
-  return MIT_OK;
-}
-
-extern "C" long mit_gemm_workspace_bytes(long M, long N, long K) {
-  long kc;
-  return max(splitk_ws_bytes(M, N, splitk_plan(M, N, K, &kc)),
-             splitk_ws_bytes(M, N, splitk_plan(M, N, K, &kc, MIT_K_CONTIG)));
-}
-
-extern "C" int mit_gemm_plan(const mit_gemm_args* g, int* ksplit) {
-  if (ksplit) *ksplit = 1;
-  if (!g || g->M <= 0 || g->N <= 0) return 0;
-  if (g->dtype != MIT_BF16) return 64;
-  if (g->argmax_keys) return 128;
-  const Split sp = plan_split(g);
-  if (ksplit) *ksplit = sp.ks;
-  if (sp.ks == 1 && use_rs(g)) return 65;  // the 64x64 register-streaming kernel
-  const bool big = sp.ks == 1 && (use_256(g->M, g->N, g->K, g->a_layout, g->tiles) || g->ln_stats || g->stats_out) &&
-                   epi_kind(g) != EK_GENERIC && (g->act == MIT_ACT_NONE || (!g->residual && !g->aux));
-  return big ? 256 : 128;
-}
-
-extern "C" int mit_gemm(const mit_gemm_args* g, void* stream) {
-  MIT_CHECK_ARG(g != nullptr, "mit_gemm: null args");
-  MIT_RECORD([c = *g, stream]() { return mit_gemm(&c, stream); });
-  MIT_CHECK_ARG(g->dtype == MIT_F32 || g->dtype == MIT_BF16, "mit_gemm: bad dtype %d", g->dtype);
-  MIT_CHECK_ARG(g->M >= 0 && g->N >= 0 && g->K >= 0, "mit_gemm: negative extent");
-  MIT_CHECK_ARG(g->A && g->B && (g->C || g->argmax_keys), "mit_gemm: null operand");
-  MIT_CHECK_ARG(g->a_layout == MIT_K_CONTIG || g->a_layout == MIT_MN_CONTIG, "mit_gemm: bad a_layout");
-  MIT_CHECK_ARG(g->b_layout == MIT_K_CONTIG || g->b_layout == MIT_MN_CONTIG, "mit_gemm: bad b_layout");
-  MIT_CHECK_ARG(g->act >= MIT_ACT_NONE && g->act <= MIT_ACT_QUICK_GELU, "mit_gemm: bad act %d", g->act);
-  if (g->M == 0 || g->N == 0) return MIT_OK;
-  MIT_CHECK_ARG(g->lda >= (g->a_layout == MIT_K_CONTIG ? g->K : g->M), "mit_gemm: lda too small");
-  MIT_CHECK_ARG(g->ldb >= (g->b_layout == MIT_K_CONTIG ? g->K : g->N), "mit_gemm: ldb too small");
-  MIT_CHECK_ARG(g->ldc >= g->N, "mit_gemm: ldc too small");
-  MIT_CHECK_ARG(!g->accumulate || g->out_f32, "mit_gemm: accumulate needs an f32 output");
-  MIT_CHECK_ARG(!g->rowsum || g->dtype == MIT_F32 || (g->a_layout == MIT_MN_CONTIG && g->b_layout == MIT_MN_CONTIG),
-                "mit_gemm(bf16): rowsum is fused into the weight-gradient (MN, MN) layout only");
-  long a_bytes = 0, b_bytes = 0;
-  if (g->dtype == MIT_BF16) {
-    // 16-byte vector staging: contiguous extents and leading dims in multiples of 8 elements
-    MIT_CHECK_ARG(g->lda % 8 == 0 && g->ldb % 8 == 0, "mit_gemm(bf16): lda/ldb must be multiples of 8");
-    MIT_CHECK_ARG(g->a_layout == MIT_MN_CONTIG ? g->M % 8 == 0 : g->K % 8 == 0,
-                  "mit_gemm(bf16): A's contiguous extent must be a multiple of 8");
-    MIT_CHECK_ARG(g->b_layout == MIT_MN_CONTIG ? g->N % 8 == 0 : g->K % 8 == 0,
-                  "mit_gemm(bf16): B's contiguous extent must be a multiple of 8");
-    MIT_CHECK_ARG(al16(g->A) && al16(g->B), "mit_gemm(bf16): A/B must be 16-B aligned");
-    a_bytes = 2 * (g->a_layout == MIT_K_CONTIG ? (g->M - 1) * g->lda + g->K : (g->K - 1) * g->lda + g->M);
-    b_bytes = 2 * (g->b_layout == MIT_K_CONTIG ? (g->N - 1) * g->ldb + g->K : (g->K - 1) * g->ldb + g->N);
-    if (g->K == 0) a_bytes = b_bytes = 0;
-    MIT_CHECK_ARG(a_bytes < (1L << 31) && b_bytes < (1L << 31), "mit_gemm(bf16): operand spans >= 2 GiB");
-  }
-  if (g->argmax_keys) {
-    MIT_CHECK_ARG(g->dtype == MIT_BF16 && g->a_layout == MIT_K_CONTIG && g->b_layout == MIT_K_CONTIG && !g->C &&
-                      g->act == MIT_ACT_NONE && !g->residual && !g->aux && g->drop_p <= 0.f && g->alpha == 1.0f &&
-                      !g->rowsum && !g->accumulate && !g->ln_stats && !g->stats_out && (!g->bias || al16(g->bias)) &&
-                      ((uintptr_t)g->argmax_keys % 8) == 0 && g->N < (1L << 32),
-                  "mit_gemm: argmax_keys needs bf16 NT operands, a bias only and no C");
-  }
-  if (g->ln_stats || g->stats_out) {
-    // the LayerNorm fold / row statistics exist only in the 256 kernel's LDS-staged bf16 epilogue
-    MIT_CHECK_ARG(g->dtype == MIT_BF16 && g->a_layout == MIT_K_CONTIG && g->b_layout == MIT_K_CONTIG && !g->out_f32 &&
-                      !g->accumulate && !g->aux && g->drop_p <= 0.f && g->alpha == 1.0f && !g->rowsum && !g->workspace &&
-                      g->N % 8 == 0 && g->ldc % 8 == 0 && al16(g->C) && (!g->bias || al16(g->bias)),
-                  "mit_gemm: ln_stats / stats_out need bf16 NT operands, a bf16 output with a plain vector epilogue");
-    MIT_CHECK_ARG(!(g->ln_stats && g->stats_out), "mit_gemm: ln_stats and stats_out are exclusive");
-  }
-  if (g->ln_stats) {
-    MIT_CHECK_ARG(g->ln_colsum && al16(g->ln_colsum) && g->K % 64 == 0 && g->ln_parts == g->K / 64 && g->ln_parts <= 16 &&
-                      !g->residual && g->ln_eps >= 0.f,
-                  "mit_gemm: ln_stats needs ln_colsum (16-B aligned), K %% 64 == 0, ln_parts = K / 64 <= 16, no residual");
-  }
-  if (g->stats_out) {
-    MIT_CHECK_ARG(g->N % 64 == 0 && g->act == MIT_ACT_NONE && g->residual && g->ldr % 8 == 0 && al16(g->residual),
-                  "mit_gemm: stats_out needs N %% 64 == 0, no activation and a (16-B aligned) residual");
-  }
+Epi make_epi(const mit_gemm_args* g) {
   Epi e;
   e.ln_stats = g->ln_stats;
   e.ln_colsum = g->ln_colsum;
@@ -1991,35 +1690,323 @@ extern "C" int mit_gemm(const mit_gemm_args* g, void* stream) {
   e.vec = (g->N % 8 == 0) && (g->ldc % 8 == 0) && al16(g->C) && (!g->bias || al16(g->bias)) &&
           (!g->residual || (g->ldr % 8 == 0 && al16(g->residual))) && (!g->aux || (g->ld_aux % 8 == 0 && al16(g->aux)));
   e.argmax_keys = g->argmax_keys;
-  hipStream_t s = (hipStream_t)stream;
-  if (g->argmax_keys) {  // the 128 kernel's gathered epilogue (any N: columns >= N never enter a key)
-    e.vec = 1;
-    launch_bf16<MIT_K_CONTIG, MIT_K_CONTIG, MIT_ACT_NONE, false>(g, e, (int)a_bytes, (int)b_bytes, Split{}, s);
-    MIT_LAUNCH_CHECK("mit_gemm");
-    return MIT_OK;
+  if (g->argmax_keys) e.vec = 1;  // no C: the gathered epilogue for any N (columns >= N never enter a key)
+  return e;
+}
+
+// ---- which instances are compiled ----
+// {activation, dropout} as template parameters where the train step uses the combination (NT operands),
+// else the generic run-time instance
+enum EpiKind { EK_PLAIN, EK_RELU, EK_RELU_DROP, EK_GELU, EK_QGELU, EK_GENERIC };
+struct EpiInst {
+  int act;
+  bool drop;
+};
+constexpr EpiInst KIND_INST[] = {{MIT_ACT_NONE, false}, {MIT_ACT_RELU, false},       {MIT_ACT_RELU, true},
+                                 {MIT_ACT_GELU, false}, {MIT_ACT_QUICK_GELU, false}, {ACT_RT, true}};
+constexpr bool is_nt(int al, int bl) { return al == MIT_K_CONTIG && bl == MIT_K_CONTIG; }
+EpiKind epi_kind(const mit_gemm_args* g) {
+  const bool drop = g->drop_p > 0.f;
+  if (g->act == MIT_ACT_NONE && !drop) return EK_PLAIN;
+  if (!is_nt(g->a_layout, g->b_layout)) return EK_GENERIC;
+  if (g->act == MIT_ACT_RELU) return drop ? EK_RELU_DROP : EK_RELU;
+  if (drop) return EK_GENERIC;
+  return g->act == MIT_ACT_GELU ? EK_GELU : EK_QGELU;
+}
+constexpr bool has_rs(int al, int bl, EpiKind) { return is_nt(al, bl); }
+constexpr bool has_128(int al, int bl, EpiKind k) { return is_nt(al, bl) || k == EK_PLAIN || k == EK_GENERIC; }
+// the 256 kernel has no generic instance; its staged epilogues need C^T accumulators (K-contig A), a
+// residual / aux block only without an activation, the LayerNorm fold / row statistics NT operands
+constexpr bool has_256(int al, int bl, EpiKind k, int stg) {
+  if (k == EK_GENERIC || (k != EK_PLAIN && !is_nt(al, bl))) return false;
+  switch (stg) {
+    case STG_REG: return true;
+    case STG_STAGED: return al == MIT_K_CONTIG;
+    case STG_STAGED_OPS: return al == MIT_K_CONTIG && KIND_INST[k].act == MIT_ACT_NONE;
+    case STG_LN_FOLD: return is_nt(al, bl) && !KIND_INST[k].drop;
+    case STG_ROW_STATS: return is_nt(al, bl) && KIND_INST[k].act == MIT_ACT_NONE;
   }
-  if (g->dtype == MIT_BF16) {
-    const int ab = (int)a_bytes, bb = (int)b_bytes;
-    const Split sp = plan_split(g);
-    const bool big = sp.ks == 1 && (use_256(g->M, g->N, g->K, g->a_layout, g->tiles) || g->ln_stats || g->stats_out);
-    if (g->a_layout == 0 && g->b_layout == 0) launch_layout<0, 0>(g, e, ab, bb, sp, big, s);
-    else if (g->a_layout == 0 && g->b_layout == 1) launch_layout<0, 1>(g, e, ab, bb, sp, big, s);
-    else if (g->a_layout == 1 && g->b_layout == 0) launch_layout<1, 0>(g, e, ab, bb, sp, big, s);
-    else launch_layout<1, 1>(g, e, ab, bb, sp, big, s);
-    if (sp.ks > 1) {
-      MIT_LAUNCH_CHECK("mit_gemm");
-      const long total = g->M * (g->N / 4);
-      long blocks = (total + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(gemm_splitk_reduce, dim3((unsigned)blocks), dim3(256), 0, s, g->M, g->N, sp.ks,
-                         (const float*)((char*)g->workspace + WS_HDR), g->C, g->ldc, g->alpha, g->out_f32,
-                         g->accumulate, g->rowsum);
+  return false;
+}
+constexpr bool has_256w(int al, int bl, EpiKind k, int stg) {
+  return is_nt(al, bl) && !KIND_INST[k].drop && (stg == STG_STAGED || stg == STG_LN_FOLD || stg == STG_ROW_STATS) &&
+         has_256(al, bl, k, stg);
+}
+
+// run-time value -> template argument: f(std::integral_constant<T, V>) for the listed V equal to v
+// (validated values: the last V otherwise)
+template <auto V, auto... VS, typename T, typename F>
+int for_value(T v, F&& f) {
+  if constexpr (sizeof...(VS) > 0)
+    if (v != (T)V) return for_value<VS...>(v, f);
+  return f(std::integral_constant<T, (T)V>{});
+}
+
+// ---- the plan ----
+// split-K (128 kernel): the workspace's first WS_HDR bytes hold the in-launch combine's per-tile
+// counters; slabs follow
+constexpr long WS_HDR = 4096;
+struct Split {
+  int ks = 1;
+  long kchunk = 0;
+};
+Split plan_split(const mit_gemm_args* g) {
+  Split p;
+  p.kchunk = g->K;
+  if (!g->workspace || !al16(g->workspace)) return p;
+  // plain epilogues only: splitting the decoder's long-K GEMMs that carry a bias / residual (fc2 forward,
+  // the fc1 / self_in data gradients; the reduce applying them) cost 1.8 % of the step (12639 / 12702 vs
+  // 12885 / 12898 pairs/s): their extra workgroups and reduce launches take CUs from the encoder prefetch
+  const bool plain = !g->bias && g->act == MIT_ACT_NONE && !g->residual && !g->aux && g->drop_p <= 0.f;
+  long kc;
+  if (plain && g->ldc % 4 == 0 && al16(g->C)) {
+    const int s = splitk_plan(g->M, g->N, g->K, &kc);
+    if (s > 1 && splitk_ws_bytes(g->M, g->N, s) <= g->workspace_bytes) {
+      p.ks = s;
+      p.kchunk = kc;
     }
-  } else {
-    if (g->a_layout == 0 && g->b_layout == 0) launch_f32<0, 0>(g, e, s);
-    else if (g->a_layout == 0 && g->b_layout == 1) launch_f32<0, 1>(g, e, s);
-    else if (g->a_layout == 1 && g->b_layout == 0) launch_f32<1, 0>(g, e, s);
-    else launch_f32<1, 1>(g, e, s);
+  }
+  return p;
+}
+
+// Occupancy-quantised cost model: the 128x128 kernel runs 2 blocks per CU, the 256x256 kernel 1;
+// a "round" fills every slot once, and a round of the 256 kernel moves 4 tiles' worth of 128x128
+// work per CU-slot at REL256 x the 128 kernel's per-FLOP speed (tools/gemm_bench.py).
+bool cost_prefers_256(long M, long N) {
+  const double REL256 = 1.3, CUS = 256.0;
+  const double t128 = (double)(((M + 127) / 128) * ((N + 127) / 128));
+  const double t256 = (double)(((M + 255) / 256) * ((N + 255) / 256));
+  const double c128 = std::ceil(t128 / (2 * CUS));             // rounds of 2 concurrent 128-tiles per CU
+  const double c256 = std::ceil(t256 / CUS) * 2.0 / REL256;    // one 256-tile = 4 128-tiles on 1 slot of 2
+  return c256 < c128;
+}
+
+enum Family { FAM_F32, FAM_RS, FAM_128, FAM_256, FAM_256W };
+constexpr int FAMILY_TILE[] = {64, 65, 128, 256, 256};  // mit_gemm_plan's return codes
+struct GemmLaunch {
+  Family fam = FAM_128;
+  EpiKind kind = EK_PLAIN;  // the <ACT, DROP> instance (KIND_INST)
+  int stg = STG_REG;        // 256 kernels
+  Split sp;                 // 128 kernel
+};
+
+// The kernel mit_gemm launches for these (validated) args. No allocation and no HIP call: recorded
+// programs replay through here on every step.
+GemmLaunch plan_gemm(const mit_gemm_args* g, const Epi& e) {
+  GemmLaunch p;
+  p.sp.kchunk = g->K;
+  if (g->dtype != MIT_BF16) {
+    p.fam = FAM_F32;
+    return p;
+  }
+  if (g->argmax_keys) return p;  // the 128 kernel's gathered epilogue folds the row argmax
+  const int al = g->a_layout, bl = g->b_layout, v = g_variant;
+  p.kind = epi_kind(g);
+  p.sp = plan_split(g);
+  if (p.sp.ks > 1) return p;  // split-K is the 128 kernel's (plain epilogue: EK_PLAIN)
+  const bool ln = g->ln_stats || g->stats_out;  // the LayerNorm fold / row statistics: 256 kernel only
+
+  // register-streaming kernel (gemm_rs_kernel): the decode step's B-row GEMMs (M <= 256) with a short
+  // K and N <= 2048 -- 7.2 vs 9.9 us per launch on 256 x {512, 1536, 2048} x 512. Everywhere else it
+  // loses: each wave streams its own A and B fragments from L2 (8 FLOP per L2 byte vs 64 for the 128
+  // kernel's LDS tiles): 2.5-3x slower on the M = 4032 decoder shapes, 2x on the decode fc_out
+  // (tools/blas_reference.py)
+  if (has_rs(al, bl, p.kind) && !g->rowsum && !ln &&
+      (v == 3 || ((v == 0 || v == 4) && g->M <= 256 && g->N <= 2048 && g->K <= 1024))) {
+    p.fam = FAM_RS;
+    return p;
+  }
+
+  // 256 kernel: asked for (variant 2, tiles = 256: the caller runs other work beside this launch) or
+  // cheaper by the cost model; never under variant 1 / tiles = 128, on small problems, or with an
+  // MN-contig A (weight gradients: those instances exceed 256 VGPRs and spill; 128 kernel + split-K)
+  const bool big = ln || v == 2 ||
+                   (v != 1 && al == MIT_K_CONTIG && g->M >= 256 && g->N >= 256 && g->K >= 128 && g->tiles != 128 &&
+                    (g->tiles == 256 || cost_prefers_256(g->M, g->N)));
+  // ... where it has the instance; its activation instances take no residual / aux operand (XOPS)
+  if (!big || !has_256(al, bl, p.kind, STG_REG) || (g->act != MIT_ACT_NONE && (g->residual || g->aux))) return p;
+  p.fam = FAM_256;
+  const bool staged = epi_gatherable(e) && !e.out_f32;
+  const int stg = e.ln_stats    ? STG_LN_FOLD
+                  : e.stats_out ? STG_ROW_STATS
+                  : !staged     ? STG_REG
+                                : (e.res || e.aux ? STG_STAGED_OPS : STG_STAGED);
+  if (has_256(al, bl, p.kind, stg)) p.stg = stg;
+  // one-wave-per-SIMD prototype (opt-in): whole K-tiles and the operand-free / statistics stages
+  if (v == 4 && g->K % BK == 0 && staged && has_256w(al, bl, p.kind, stg)) p.fam = FAM_256W;
+  return p;
+}
+
+// ---- one launcher per kernel family ----
+template <int AL, int BL>
+void launch_f32(const mit_gemm_args* g, const Epi& e, hipStream_t s) {
+  dim3 grid((unsigned)((g->N + 63) / 64), (unsigned)((g->M + 63) / 64));
+  hipLaunchKernelGGL((gemm_f32_kernel<AL, BL>), grid, dim3(256), 0, s, (const float*)g->A, (const float*)g->B, g->C, g->M,
+                     g->N, g->K, g->lda, g->ldb, g->ldc, e, g->rowsum);
+}
+
+// the bf16 kernels share their leading arguments; `tail` is the family's own
+template <auto KERNEL, int THREADS, int LDS, typename... Tail>
+void launch_bf16(long blocks, const mit_gemm_args* g, const Epi& e, int a_bytes, int b_bytes, hipStream_t s, Tail... tail) {
+  static const bool lds = set_lds(KERNEL, LDS);
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)blocks), dim3(THREADS), LDS, s, (const bf16*)g->A, (const bf16*)g->B, g->C,
+                     g->M, g->N, g->K, g->lda, g->ldb, g->ldc, a_bytes, b_bytes, e, tail...);
+}
+inline long blocks_of(const mit_gemm_args* g, long edge) { return ((g->M + edge - 1) / edge) * ((g->N + edge - 1) / edge); }
+
+template <EpiKind KIND>
+void launch_rs(const mit_gemm_args* g, const Epi& e, int ab, int bb, hipStream_t s) {
+  launch_bf16<gemm_rs_kernel<KIND_INST[KIND].act, KIND_INST[KIND].drop>, 256, RS_SMEM>(blocks_of(g, 64), g, e, ab, bb, s);
+}
+// 8 waves per 128x128 block (2 per SIMD, each issuing half the LDS-DMA pieces of a K-tile): with 4
+// waves every K-tile's 8 DMA pieces per wave sat serially in front of its 32 MFMAs (+2.7 % step)
+template <int AL, int BL, EpiKind KIND>
+void launch_128(const mit_gemm_args* g, const Epi& e, int ab, int bb, const Split& sp, hipStream_t s) {
+  float* ws = g->workspace ? (float*)((char*)g->workspace + WS_HDR) : nullptr;
+  launch_bf16<gemm_bf16_kernel<AL, BL, KIND_INST[KIND].act, KIND_INST[KIND].drop>, 512, smem_bytes(2)>(
+      blocks_of(g, BM) * sp.ks, g, e, ab, bb, s, sp.ks, sp.kchunk, ws, g->rowsum);
+}
+template <int AL, int BL, EpiKind KIND, int STG>
+void launch_256(const mit_gemm_args* g, const Epi& e, int ab, int bb, hipStream_t s) {
+  launch_bf16<gemm256_kernel<AL, BL, KIND_INST[KIND].act, KIND_INST[KIND].drop, STG>, 512,
+              STG == STG_REG ? SMEM2_BYTES : SMEM2_EPI_BYTES>(blocks_of(g, B2), g, e, ab, bb, s, (float*)g->workspace,
+                                                             g->rowsum);
+}
+template <EpiKind KIND, int STG>
+void launch_256w(const mit_gemm_args* g, const Epi& e, int ab, int bb, hipStream_t s) {
+  launch_bf16<gemm256w_kernel<KIND_INST[KIND].act, STG>, 256, SMEM2_EPI_BYTES>(blocks_of(g, B2), g, e, ab, bb, s);
+}
+
+int no_instance() {
+  mit_set_error("mit_gemm: the plan names a kernel instance that is not compiled");
+  return MIT_ERR_INVALID;
+}
+
+int launch_gemm(const GemmLaunch& p, const mit_gemm_args* g, const Epi& e, int ab, int bb, hipStream_t s) {
+  return for_value<MIT_K_CONTIG, MIT_MN_CONTIG>(g->a_layout, [&](auto al) {
+    return for_value<MIT_K_CONTIG, MIT_MN_CONTIG>(g->b_layout, [&](auto bl) {
+      constexpr int AL = decltype(al)::value, BL = decltype(bl)::value;
+      if (p.fam == FAM_F32) return launch_f32<AL, BL>(g, e, s), MIT_OK;
+      return for_value<EK_PLAIN, EK_RELU, EK_RELU_DROP, EK_GELU, EK_QGELU, EK_GENERIC>(p.kind, [&](auto kind) {
+        constexpr EpiKind KIND = decltype(kind)::value;
+        if (p.fam == FAM_RS) {
+          if constexpr (has_rs(AL, BL, KIND)) return launch_rs<KIND>(g, e, ab, bb, s), MIT_OK;
+        } else if (p.fam == FAM_128) {
+          if constexpr (has_128(AL, BL, KIND)) return launch_128<AL, BL, KIND>(g, e, ab, bb, p.sp, s), MIT_OK;
+        } else {
+          return for_value<STG_REG, STG_STAGED, STG_STAGED_OPS, STG_LN_FOLD, STG_ROW_STATS>(p.stg, [&](auto stg) {
+            constexpr int STG = decltype(stg)::value;
+            if (p.fam == FAM_256) {
+              if constexpr (has_256(AL, BL, KIND, STG)) return launch_256<AL, BL, KIND, STG>(g, e, ab, bb, s), MIT_OK;
+            } else {
+              if constexpr (has_256w(AL, BL, KIND, STG)) return launch_256w<KIND, STG>(g, e, ab, bb, s), MIT_OK;
+            }
+            return no_instance();
+          });
+        }
+        return no_instance();
+      });
+    });
+  });
+}
+
+// everything mit_gemm rejects; the operands' byte spans for the bf16 kernels' buffer resources
+int validate_gemm(const mit_gemm_args* g, int* a_span, int* b_span) {
+  MIT_CHECK_ARG(g->dtype == MIT_F32 || g->dtype == MIT_BF16, "mit_gemm: bad dtype %d", g->dtype);
+  MIT_CHECK_ARG(g->M >= 0 && g->N >= 0 && g->K >= 0, "mit_gemm: negative extent");
+  MIT_CHECK_ARG(g->A && g->B && (g->C || g->argmax_keys), "mit_gemm: null operand");
+  MIT_CHECK_ARG(g->a_layout == MIT_K_CONTIG || g->a_layout == MIT_MN_CONTIG, "mit_gemm: bad a_layout");
+  MIT_CHECK_ARG(g->b_layout == MIT_K_CONTIG || g->b_layout == MIT_MN_CONTIG, "mit_gemm: bad b_layout");
+  MIT_CHECK_ARG(g->act >= MIT_ACT_NONE && g->act <= MIT_ACT_QUICK_GELU, "mit_gemm: bad act %d", g->act);
+  if (g->M == 0 || g->N == 0) return MIT_OK;  // nothing to launch: the rest is not checked
+  MIT_CHECK_ARG(g->lda >= (g->a_layout == MIT_K_CONTIG ? g->K : g->M), "mit_gemm: lda too small");
+  MIT_CHECK_ARG(g->ldb >= (g->b_layout == MIT_K_CONTIG ? g->K : g->N), "mit_gemm: ldb too small");
+  MIT_CHECK_ARG(g->ldc >= g->N, "mit_gemm: ldc too small");
+  MIT_CHECK_ARG(!g->accumulate || g->out_f32, "mit_gemm: accumulate needs an f32 output");
+  MIT_CHECK_ARG(!g->rowsum || g->dtype == MIT_F32 || (g->a_layout == MIT_MN_CONTIG && g->b_layout == MIT_MN_CONTIG),
+                "mit_gemm(bf16): rowsum is fused into the weight-gradient (MN, MN) layout only");
+  long a_bytes = 0, b_bytes = 0;
+  if (g->dtype == MIT_BF16) {
+    // 16-byte vector staging: contiguous extents and leading dims in multiples of 8 elements
+    MIT_CHECK_ARG(g->lda % 8 == 0 && g->ldb % 8 == 0, "mit_gemm(bf16): lda/ldb must be multiples of 8");
+    MIT_CHECK_ARG(g->a_layout == MIT_MN_CONTIG ? g->M % 8 == 0 : g->K % 8 == 0,
+                  "mit_gemm(bf16): A's contiguous extent must be a multiple of 8");
+    MIT_CHECK_ARG(g->b_layout == MIT_MN_CONTIG ? g->N % 8 == 0 : g->K % 8 == 0,
+                  "mit_gemm(bf16): B's contiguous extent must be a multiple of 8");
+    MIT_CHECK_ARG(al16(g->A) && al16(g->B), "mit_gemm(bf16): A/B must be 16-B aligned");
+    a_bytes = 2 * (g->a_layout == MIT_K_CONTIG ? (g->M - 1) * g->lda + g->K : (g->K - 1) * g->lda + g->M);
+    b_bytes = 2 * (g->b_layout == MIT_K_CONTIG ? (g->N - 1) * g->ldb + g->K : (g->K - 1) * g->ldb + g->N);
+    if (g->K == 0) a_bytes = b_bytes = 0;
+    MIT_CHECK_ARG(a_bytes < (1L << 31) && b_bytes < (1L << 31), "mit_gemm(bf16): operand spans >= 2 GiB");
+  }
+  *a_span = (int)a_bytes;
+  *b_span = (int)b_bytes;
+  if (g->argmax_keys) {
+    MIT_CHECK_ARG(g->dtype == MIT_BF16 && g->a_layout == MIT_K_CONTIG && g->b_layout == MIT_K_CONTIG && !g->C &&
+                      g->act == MIT_ACT_NONE && !g->residual && !g->aux && g->drop_p <= 0.f && g->alpha == 1.0f &&
+                      !g->rowsum && !g->accumulate && !g->ln_stats && !g->stats_out && (!g->bias || al16(g->bias)) &&
+                      ((uintptr_t)g->argmax_keys % 8) == 0 && g->N < (1L << 32),
+                  "mit_gemm: argmax_keys needs bf16 NT operands, a bias only and no C");
+  }
+  if (g->ln_stats || g->stats_out) {
+    // the LayerNorm fold / row statistics exist only in the 256 kernel's LDS-staged bf16 epilogue
+    MIT_CHECK_ARG(g->dtype == MIT_BF16 && g->a_layout == MIT_K_CONTIG && g->b_layout == MIT_K_CONTIG && !g->out_f32 &&
+                      !g->accumulate && !g->aux && g->drop_p <= 0.f && g->alpha == 1.0f && !g->rowsum && !g->workspace &&
+                      g->N % 8 == 0 && g->ldc % 8 == 0 && al16(g->C) && (!g->bias || al16(g->bias)),
+                  "mit_gemm: ln_stats / stats_out need bf16 NT operands, a bf16 output with a plain vector epilogue");
+    MIT_CHECK_ARG(!(g->ln_stats && g->stats_out), "mit_gemm: ln_stats and stats_out are exclusive");
+  }
+  if (g->ln_stats) {
+    MIT_CHECK_ARG(g->ln_colsum && al16(g->ln_colsum) && g->K % 64 == 0 && g->ln_parts == g->K / 64 && g->ln_parts <= 16 &&
+                      !g->residual && g->ln_eps >= 0.f,
+                  "mit_gemm: ln_stats needs ln_colsum (16-B aligned), K %% 64 == 0, ln_parts = K / 64 <= 16, no residual");
+  }
+  if (g->stats_out) {
+    MIT_CHECK_ARG(g->N % 64 == 0 && g->act == MIT_ACT_NONE && g->residual && g->ldr % 8 == 0 && al16(g->residual),
+                  "mit_gemm: stats_out needs N %% 64 == 0, no activation and a (16-B aligned) residual");
+  }
+  return MIT_OK;
+}
+
+}  // namespace
+
+extern "C" int mit_gemm_set_variant(int v) {
+  MIT_CHECK_ARG(v >= 0 && v <= 4, "mit_gemm_set_variant: %d not in {0,1,2,3,4}", v);
+  g_variant = v;
+  return MIT_OK;
+}
+
+extern "C" long mit_gemm_workspace_bytes(long M, long N, long K) {
+  long kc;
+  return splitk_ws_bytes(M, N, splitk_plan(M, N, K, &kc));
+}
+
+extern "C" int mit_gemm_plan(const mit_gemm_args* g, int* ksplit) {
+  if (ksplit) *ksplit = 1;
+  if (!g || g->M <= 0 || g->N <= 0) return 0;
+  const GemmLaunch p = plan_gemm(g, make_epi(g));
+  if (ksplit) *ksplit = p.sp.ks;
+  return FAMILY_TILE[p.fam];
+}
+
+extern "C" int mit_gemm(const mit_gemm_args* g, void* stream) {
+  MIT_CHECK_ARG(g != nullptr, "mit_gemm: null args");
+  MIT_RECORD([c = *g, stream]() { return mit_gemm(&c, stream); });
+  int a_bytes = 0, b_bytes = 0;
+  if (const int rc = validate_gemm(g, &a_bytes, &b_bytes)) return rc;
+  if (g->M == 0 || g->N == 0) return MIT_OK;
+  const Epi e = make_epi(g);
+  const GemmLaunch p = plan_gemm(g, e);
+  hipStream_t s = (hipStream_t)stream;
+  if (const int rc = launch_gemm(p, g, e, a_bytes, b_bytes, s)) return rc;
+  if (p.sp.ks > 1) {  // the slabs' combine applies alpha / accumulate and sums the row-sum partials
+    MIT_LAUNCH_CHECK("mit_gemm");
+    const long total = g->M * (g->N / 4);
+    long blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(gemm_splitk_reduce, dim3((unsigned)blocks), dim3(256), 0, s, g->M, g->N, p.sp.ks,
+                       (const float*)((char*)g->workspace + WS_HDR), g->C, g->ldc, g->alpha, g->out_f32,
+                       g->accumulate, g->rowsum);
   }
   MIT_LAUNCH_CHECK("mit_gemm");
   return MIT_OK;
@@ -2029,25 +2016,35 @@ extern "C" int mit_gemm(const mit_gemm_args* g, void* stream) {
 // for the cross-K/V + projection pair) no split: 12482-12503 pairs/s vs 12278-12433 with 2 (two blocks
 // per CU), 12232-12263 with 3, 12081-12153 with 4 (interleaved, one box); the fp32 slabs and their
 // combine cost more than the shorter K loops save once the group fills the chip.
-long grouped_split(long tiles) {
+static long grouped_split(const mit_gemm_args* args, int n) {
+  long tiles = 0;
+  for (int i = 0; i < n; ++i) tiles += blocks_of(args + i, BM);
   return tiles > 0 ? max(1L, min(16L, (long)num_cus() / tiles)) : 1;
+}
+
+// One problem's share of the group factor s: its split factor (K-chunks of at least 512), the chunk
+// rounded up to whole K-tiles, and its slab bytes (0: no split). The slab is sized for the factor before
+// that rounding -- what mit_gemm_grouped_ws_bytes has always returned -- and the rounding can only lower
+// the factor the launch runs with, so a launch never needs more than the size it was given.
+struct GroupSplit {
+  long si, kchunk, slab_bytes;
+};
+static GroupSplit grouped_problem_split(const mit_gemm_args& g, long s) {
+  const long s0 = max(1L, min(s, g.K / 512));
+  const long kc = max((long)BK, ((g.K + s0 - 1) / s0 + BK - 1) / BK * BK);
+  return {(g.K + kc - 1) / kc, kc, s0 > 1 ? (4L * s0 * g.M * g.N + 4L * s0 * g.M + 255) / 256 * 256 : 0};
 }
 
 extern "C" long mit_gemm_grouped_ws_bytes(const mit_gemm_args* args, int n) {
   if (!args || n <= 0 || n > MAXG) return 0;
-  long tiles = 0;
-  for (int i = 0; i < n; ++i) tiles += ((args[i].M + BM - 1) / BM) * ((args[i].N + BN - 1) / BN);
-  long s = grouped_split(tiles);
+  const long s = grouped_split(args, n);
   long bytes = WS_HDR;
-  for (int i = 0; i < n; ++i) {
-    const long si = max(1L, min(s, args[i].K / 512));
-    bytes += si > 1 ? (4L * si * args[i].M * args[i].N + 4L * si * args[i].M + 255) / 256 * 256 : 0;
-  }
+  for (int i = 0; i < n; ++i) bytes += grouped_problem_split(args[i], s).slab_bytes;
   return bytes;
 }
 
-// Grouped dW launch (see gemm_bf16_grouped): split-K factor chosen for the group (about two blocks
-// per CU over all problems), slabs of problem i at consecutive 256-B aligned offsets of workspace.
+// Grouped dW launch (see gemm_bf16_grouped): split-K factor chosen for the group (grouped_split), slabs
+// of problem i at consecutive 256-B aligned offsets of workspace.
 extern "C" int mit_gemm_grouped(const mit_gemm_args* args, int n, const mit_ln_grads_job* ln, int n_ln,
                                 void* workspace, long workspace_bytes, void* stream) {
   MIT_CHECK_ARG(args && n >= 1 && n <= MAXG, "mit_gemm_grouped: 1..%d problems", MAXG);
@@ -2062,7 +2059,6 @@ extern "C" int mit_gemm_grouped(const mit_gemm_args* args, int n, const mit_ln_g
   MIT_CHECK_ARG(workspace_bytes >= mit_gemm_grouped_ws_bytes(args, n) && (workspace || workspace_bytes == 0) &&
                     al16(workspace),
                 "mit_gemm_grouped: workspace too small (%ld < %ld)", workspace_bytes, mit_gemm_grouped_ws_bytes(args, n));
-  long tiles = 0;
   for (int i = 0; i < n; ++i) {
     const mit_gemm_args* g = args + i;
     MIT_CHECK_ARG(g->dtype == MIT_BF16 && g->a_layout == MIT_MN_CONTIG && g->b_layout == MIT_MN_CONTIG,
@@ -2075,9 +2071,8 @@ extern "C" int mit_gemm_grouped(const mit_gemm_args* args, int n, const mit_ln_g
                   "mit_gemm_grouped: problem %d: extents / alignment", i);
     MIT_CHECK_ARG(2 * ((g->K - 1) * g->lda + g->M) < (1L << 31) && 2 * ((g->K - 1) * g->ldb + g->N) < (1L << 31),
                   "mit_gemm_grouped: problem %d: operand spans >= 2 GiB", i);
-    tiles += ((g->M + BM - 1) / BM) * ((g->N + BN - 1) / BN);
   }
-  const long s = grouped_split(tiles);
+  const long s = grouped_split(args, n);
   GroupArgs ga;
   ga.n = n;
   int start = 0, rstart = 0;
@@ -2092,17 +2087,15 @@ extern "C" int mit_gemm_grouped(const mit_gemm_args* args, int n, const mit_ln_g
     q.M = g->M; q.N = g->N; q.K = g->K; q.lda = g->lda; q.ldb = g->ldb; q.ldc = g->ldc;
     q.a_bytes = (int)(2 * ((g->K - 1) * g->lda + g->M));
     q.b_bytes = (int)(2 * ((g->K - 1) * g->ldb + g->N));
-    long si = max(1L, min(s, g->K / 512));
-    long kc = (g->K + si - 1) / si;
-    kc = (kc + BK - 1) / BK * BK;
-    si = (g->K + kc - 1) / kc;
+    const GroupSplit gs = grouped_problem_split(*g, s);
+    const long si = gs.si;
     q.ksplit = (int)si;
-    q.kchunk = kc;
+    q.kchunk = gs.kchunk;
     q.rowsum = g->rowsum;
     q.ws = nullptr;
     if (si > 1) {
       q.ws = (float*)wsp;
-      wsp += (4L * si * g->M * g->N + 4L * si * g->M + 255) / 256 * 256;
+      wsp += gs.slab_bytes;
       any_split = true;
     }
     Epi& e = q.e;
@@ -2113,17 +2106,13 @@ extern "C" int mit_gemm_grouped(const mit_gemm_args* args, int n, const mit_ln_g
     e.accumulate = g->accumulate;
     e.vec = (g->N % 8 == 0) && (g->ldc % 8 == 0) && al16(g->C);
     q.start = start;
-    start += (int)(((g->M + BM - 1) / BM) * ((g->N + BN - 1) / BN) * si);
+    start += (int)(blocks_of(g, BM) * si);
     q.rblocks = si > 1 ? (int)min(1024L, (g->M * (g->N / 4) + 255) / 256) : 0;
     q.rstart = rstart;
     rstart += q.rblocks;
   }
   hipStream_t st = (hipStream_t)stream;
-  static bool attr = false;
-  if (!attr) {
-    set_lds(gemm_bf16_grouped, smem_bytes(2));
-    attr = true;
-  }
+  static const bool lds = set_lds(gemm_bf16_grouped, smem_bytes(2));
   // deal the tiles to the XCDs: problem after problem, at most cap per XCD
   const int cap = (start + 7) / 8;
   int np = 0, xc = 0, used = 0;

@@ -19,7 +19,7 @@ def main():
     dev = torch.device("cuda", 0)
 
     class A:
-        vocab, memory_mode, dtype = 10000, "patches", "bf16"
+        vocab, memory_mode, dtype, workload = 10000, "patches", "bf16", "train"
     model, opt = bench.build(A, 0)
     model.train()
     images, di, tg = bench.synthetic_batch(64, 64, 10000, dev, 1000)
