@@ -70,6 +70,7 @@ int mit_stream_wait_event(void* stream, void* event);
  *   B(k,n) = B[n*ldb+k] (b_layout K_CONTIG) or B[k*ldb+n] (MN_CONTIG)
  *   auxmask: if aux != NULL, multiply by (aux[m*ld_aux+n] > 0 ? aux_scale : 0)  (ReLU/dropout bwd)
  *   dropout index = m*N + n ; residual/aux in the operand dtype; bias f32 [N]
+ *   residual != NULL needs ldr >= N, aux != NULL needs ld_aux >= N (rejected otherwise; ignored when NULL)
  *   out_f32: write f32 (accumulate: C += value), else the operand dtype.
  *   rowsum (optional, f32 [M]): rowsum[m] = sum_k A(m,k) — the bias gradient when A = dY^T in a
  *     weight-gradient GEMM, fused in (no separate column-sum pass over dY).

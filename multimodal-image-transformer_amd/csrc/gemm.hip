@@ -1922,6 +1922,8 @@ int validate_gemm(const mit_gemm_args* g, int* a_span, int* b_span) {
   MIT_CHECK_ARG(g->lda >= (g->a_layout == MIT_K_CONTIG ? g->K : g->M), "mit_gemm: lda too small");
   MIT_CHECK_ARG(g->ldb >= (g->b_layout == MIT_K_CONTIG ? g->K : g->N), "mit_gemm: ldb too small");
   MIT_CHECK_ARG(g->ldc >= g->N, "mit_gemm: ldc too small");
+  MIT_CHECK_ARG(!g->residual || g->ldr >= g->N, "mit_gemm: ldr too small");
+  MIT_CHECK_ARG(!g->aux || g->ld_aux >= g->N, "mit_gemm: ld_aux too small");
   MIT_CHECK_ARG(!g->accumulate || g->out_f32, "mit_gemm: accumulate needs an f32 output");
   MIT_CHECK_ARG(!g->rowsum || g->dtype == MIT_F32 || (g->a_layout == MIT_MN_CONTIG && g->b_layout == MIT_MN_CONTIG),
                 "mit_gemm(bf16): rowsum is fused into the weight-gradient (MN, MN) layout only");

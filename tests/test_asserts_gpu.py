@@ -2,7 +2,8 @@
 "kernel bounds asserts behind a flag"; `make -C multimodal-image-transformer_amd/csrc asserts` ->
 lib/diag/libmit_hip_asserts.so): every GEMM tile kernel (256, 128 + split-K, register-streaming, f32)
 and the attention kernels (head-resident forward, 64-query forward, fused backward) run under it with
-ragged extents and return the same results as the shipped build -- no assert fires. Runs in a child
+ragged extents (the GEMM kernels also with leading dimensions above the extents) and return the same
+results as the shipped build -- no assert fires. Runs in a child
 process (the library is loaded once per process, selected by MIT_LIB)."""
 import os
 import subprocess
@@ -38,6 +39,20 @@ for (M, Nn, K, al, bl) in [(520, 776, 200, 0, 0), (1000, 520, 136, 0, 1), (264, 
     C32 = torch.empty(M, Nn, device=dev)
     N.gemm(A.to(dev), B.to(dev), C32, M, Nn, K, a_layout=al, b_layout=bl)
     assert rel(C32.cpu(), ref) < 1e-5
+# leading dimensions above the extents (the asserts see ld > extent): the 128, 256 and register-streaming
+# kernels with lda = K + 8, ldb = K + 16, ldc = N + 8, the f32 kernel with + 3 / + 5 / + 2
+def padded(x, ld, dt):
+    p = torch.zeros(x.shape[0], ld, device=dev, dtype=dt)
+    p[:, :x.shape[1]] = x.to(dev, dt)
+    return p
+for (M, Nn, K, v, dt, pa, pb, pc) in [(136, 136, 72, 1, torch.bfloat16, 8, 16, 8), (264, 264, 72, 2, torch.bfloat16, 8, 16, 8),
+                                      (70, 72, 136, 3, torch.bfloat16, 8, 16, 8), (70, 72, 136, 0, torch.float32, 3, 5, 2)]:
+    A, B = torch.randn(M, K), torch.randn(Nn, K)
+    N.gemm_set_variant(v)
+    C = torch.full((M, Nn + pc), -12288.0, device=dev)
+    N.gemm(padded(A, K + pa, dt), padded(B, K + pb, dt), C, M, Nn, K, lda=K + pa, ldb=K + pb, ldc=Nn + pc)
+    assert rel(C[:, :Nn].cpu(), A @ B.t()) < (1e-2 if dt == torch.bfloat16 else 1e-5), (M, Nn, K, v)
+    assert (C[:, Nn:] == -12288.0).all(), (M, Nn, K, v)
 N.gemm_set_variant(0)
 for (Bb, H, Lq, Lk, causal) in [(3, 12, 197, 197, 0), (2, 8, 63, 197, 0), (4, 8, 63, 63, 1)]:
     D = 64
