@@ -213,8 +213,9 @@ int mit_row_stats64(long rows, long cols, const void* x, long ldx, float* out, v
  * mask is never materialised: key j of batch b is masked iff j > i (causal) or
  * key_tokens[b*tok_batch + j] == pad_idx); decoder cross-attention (no mask).
  * Element strides: X(b, t, h, :) = X + b*X_batch + t*X_row + h*Dh. lse: f32 [B*H*Lq] (log-sum-exp
- * of the scaled, masked scores; required by the backward). A fully masked row yields NaN, as in
- * the reference. */
+ * of the scaled, masked scores; required by the backward). A fully masked row yields NaN in o, as in
+ * the reference, and -inf in lse (the log of an empty sum); every other row of the call is unaffected.
+ * The backward of a call with such a row is undefined. */
 typedef struct {
   const void* q;
   long q_row, q_batch;
@@ -257,6 +258,30 @@ int mit_attention_bwd(int dtype, long B, long H, long Lq, long Lk, long Dh, cons
  * 64-bit-index kernels (forward attn_fwd_simple, backward attn_bwd_dq/dkv_mfma). A smaller limit sends
  * small calls down that path (tests/test_kernels_gpu.py); limit <= 0 restores 2^32. Process-wide. */
 int mit_attention_set_index_limit(double limit);
+
+/* The launches mit_attention_fwd / mit_attention_bwd would make for these arguments (no launch, nothing
+ * dereferenced: runs without a GPU). Both entry points and this one call the same two host decision
+ * functions (csrc/attention.hip plan_fwd / plan_bwd), and mit_attention_set_index_limit is honoured.
+ *   fwd: MIT_ATTN_GENERIC (attn_fwd_simple: f32, head_dim != 64, operands off the MFMA kernels' alignment --
+ *        q/k/v rows, batches % 8 elements and 16-B pointers, o rows, batches % 4 and an 8-B pointer -- or
+ *        dropout indices past the index limit), MIT_ATTN_FWD_MFMA (attn_fwd_mfma: causal and / or key_tokens,
+ *        or Lk > 640), MIT_ATTN_FWD_HEAD / MIT_ATTN_FWD_HEAD_DROP (attn_fwd_head without / with dropout: no
+ *        mask, Lk <= 640). fwd_nw / fwd_lkp: the head kernel's waves per workgroup (one per 16-query tile, at
+ *        most 8 with dropout or fwd_lkp <= 320, else 16) and staged key rows (Lk rounded up to 16); 0 otherwise.
+ *   bwd (g != NULL; -1 when g is NULL): MIT_ATTN_GENERIC (attn_bwd_dq_simple + attn_bwd_dkv_simple; as the
+ *        forward's rule, with o rows, batches % 8, dout as q, dq/dk/dv as o),
+ *        MIT_ATTN_BWD_MFMA (attn_bwd_dq_mfma + attn_bwd_dkv_mfma), MIT_ATTN_BWD_HEAD (attn_bwd_head: Lq <= 64,
+ *        Lk <= 256, B*H*Lq*Lk below the index limit). bwd_nw / bwd_lkp: attn_bwd_head's 8 waves and staged
+ *        key rows (Lk rounded up to 32); 0 otherwise.
+ * For tests that must know which kernel a shape ran, and for tools that attribute kernel time. */
+enum { MIT_ATTN_GENERIC = 0, MIT_ATTN_FWD_MFMA = 1, MIT_ATTN_FWD_HEAD = 2, MIT_ATTN_FWD_HEAD_DROP = 3 };
+enum { MIT_ATTN_BWD_MFMA = 1, MIT_ATTN_BWD_HEAD = 2 };
+typedef struct {
+  int fwd, fwd_nw, fwd_lkp;
+  int bwd, bwd_nw, bwd_lkp;
+} mit_attn_plan;
+int mit_attention_plan(int dtype, long B, long H, long Lq, long Lk, long Dh, const mit_attn_args* a,
+                       const mit_attn_grads* g, mit_attn_plan* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * Encoder input assembly.

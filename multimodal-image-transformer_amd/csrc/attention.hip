@@ -1203,6 +1203,116 @@ extern "C" int mit_attention_set_index_limit(double limit) {
   return MIT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dispatch: one host decision per direction. mit_attention_fwd / mit_attention_bwd launch what these
+// return and mit_attention_plan reports it; neither dereferences an operand.
+// ------------------------------------------------------------------------------------------------
+constexpr int PLAN_SPAN = -1;  // an MFMA-eligible call whose operand span does not fit a buffer descriptor
+struct FwdPlan {
+  int family;  // MIT_ATTN_GENERIC / MIT_ATTN_FWD_*
+  int nw, lkp; // attn_fwd_head: waves per workgroup, staged key rows
+  long kb, vb; // MFMA kernels: bytes of one head's K / V rows (buffer-load bounds)
+};
+struct BwdPlan {
+  int family;  // MIT_ATTN_GENERIC / MIT_ATTN_BWD_*
+  int lkp;     // attn_bwd_head: staged key rows
+  AttnBwdBytes nb;
+};
+
+static FwdPlan plan_fwd(int dtype, long B, long H, long Lq, long Lk, long Dh, const mit_attn_args* x) {
+  FwdPlan p{MIT_ATTN_GENERIC, 0, 0, 0, 0};
+  // the MFMA kernels are written for head_dim 64 (every ViT / CLIP tower and the 512/768-wide
+  // decoders); other head dims run the generic kernels
+  const bool mfma_ok = Dh == D && dtype == MIT_BF16 && x->q_row % 8 == 0 && x->q_batch % 8 == 0 && x->k_row % 8 == 0 &&
+                       x->k_batch % 8 == 0 && x->v_row % 8 == 0 && x->v_batch % 8 == 0 && x->o_row % 4 == 0 &&
+                       x->o_batch % 4 == 0 && ((uintptr_t)x->q | (uintptr_t)x->k | (uintptr_t)x->v) % 16 == 0 &&
+                       ((uintptr_t)x->o % 8) == 0;
+  if (!mfma_ok) return p;
+  p.kb = 2 * ((Lk - 1) * x->k_row + D);
+  p.vb = 2 * ((Lk - 1) * x->v_row + D);
+  if (p.kb >= (1L << 31) || p.vb >= (1L << 31)) {
+    p.family = PLAN_SPAN;
+    return p;
+  }
+  const bool dropout = x->drop_p > 0.f;
+  // dropout indices past 2^32 run the generic kernel (the MFMA kernels form them in 32 bits)
+  const bool idx32 = !dropout || (double)B * (double)H * (double)Lq * (double)Lk < g_idx32_limit;
+  if (!x->causal && !x->key_tokens && Lk <= HK_MAX && H <= 65535 && B <= 65535 && idx32) {
+    // head-resident K/V: one workgroup per (b, h), NW waves balanced over the 16-query tiles.
+    // K/V rows are staged to a multiple of 16 (the key tail of < 64 runs 16-key tiles: a ViT-B/16
+    // head of 197 keys sweeps 208 instead of 256; 28.5 -> 27.7 us, tools/attn_bench.py). <= 8 waves
+    // whenever two heads fit the LDS, so a CU holds two workgroups and one stages its K/V while the
+    // other computes. Three 5-wave workgroups per CU (one round of the 768 heads instead of 1.5,
+    // 52 KiB each) measured slower (30.8 us): the CU's VALU, not the rounds, bounds this kernel.
+    // The dropout instance is built for <= 512 threads.
+    constexpr int pad = 16;
+    p.lkp = (int)((Lk + pad - 1) / pad * pad);
+    const int nqt = (int)((Lq + 15) / 16);
+    const int maxw = (dropout || 2 * p.lkp * 256 <= 160 * 1024) ? 8 : 16;
+    // every wave the occupancy allows, the query tiles' rounds unbalanced (CLIP-L/14@336: 37 = 16 + 16 + 5
+    // in one workgroup per CU; ViT-B/16: 13 = 8 + 5 in two) rather than fewer balanced waves (13 + 13 + 11,
+    // 7 + 6): more waves to hide the sweep's latency, 47.2 -> 45.2 / 26.7 -> 26.5 us, configs[2]
+    // 2067 -> 2078 pairs/s (profiles/r05_decoder_experiments.txt)
+    p.nw = std::min(nqt, maxw);
+    p.family = dropout ? MIT_ATTN_FWD_HEAD_DROP : MIT_ATTN_FWD_HEAD;
+  } else if (idx32) {
+    p.family = MIT_ATTN_FWD_MFMA;
+  }
+  return p;
+}
+
+static BwdPlan plan_bwd(int dtype, long B, long H, long Lq, long Lk, long Dh, const mit_attn_args* x,
+                        const mit_attn_grads* gg) {
+  BwdPlan p{MIT_ATTN_GENERIC, 0, {0, 0, 0, 0}};
+  auto al = [](const void* ptr, int n) { return ((uintptr_t)ptr % n) == 0; };
+  const bool mfma_ok = Dh == D && dtype == MIT_BF16 && x->q_row % 8 == 0 && x->q_batch % 8 == 0 && x->k_row % 8 == 0 &&
+                       x->k_batch % 8 == 0 && x->v_row % 8 == 0 && x->v_batch % 8 == 0 && x->o_row % 8 == 0 &&
+                       x->o_batch % 8 == 0 && gg->do_row % 8 == 0 && gg->do_batch % 8 == 0 && gg->dq_row % 4 == 0 &&
+                       gg->dq_batch % 4 == 0 && gg->dk_row % 4 == 0 && gg->dk_batch % 4 == 0 && gg->dv_row % 4 == 0 &&
+                       gg->dv_batch % 4 == 0 && al(x->q, 16) && al(x->k, 16) && al(x->v, 16) && al(x->o, 16) &&
+                       al(gg->dout, 16) && al(gg->dq, 8) && al(gg->dk, 8) && al(gg->dv, 8);
+  if (!mfma_ok) return p;
+  const long qb = 2 * ((Lq - 1) * x->q_row + D), kb = 2 * ((Lk - 1) * x->k_row + D);
+  const long vb = 2 * ((Lk - 1) * x->v_row + D), db = 2 * ((Lq - 1) * gg->do_row + D);
+  if (!(qb < (1L << 31) && kb < (1L << 31) && vb < (1L << 31) && db < (1L << 31))) {
+    p.family = PLAN_SPAN;
+    return p;
+  }
+  p.nb.q = (int)qb;
+  p.nb.k = (int)kb;
+  p.nb.v = (int)vb;
+  p.nb.dO = (int)db;
+  // (the head kernel forms its dropout indices in 32 bits: B * H * Lq * Lk < 2^32)
+  if (Lq <= 64 && Lk <= HB_MAXK && H <= 65535 && B <= 65535 && x->o_row % 8 == 0 &&
+      (double)B * (double)H * (double)Lq * (double)Lk < g_idx32_limit) {
+    p.lkp = (int)((Lk + 31) / 32 * 32);
+    p.family = MIT_ATTN_BWD_HEAD;
+  } else {
+    p.family = MIT_ATTN_BWD_MFMA;
+  }
+  return p;
+}
+
+extern "C" int mit_attention_plan(int dtype, long B, long H, long Lq, long Lk, long Dh, const mit_attn_args* x,
+                                  const mit_attn_grads* gg, mit_attn_plan* out) {
+  MIT_CHECK_ARG(x && out, "mit_attention_plan: null pointer");
+  MIT_CHECK_ARG(dtype == MIT_BF16 || dtype == MIT_F32, "mit_attention_plan: bad dtype %d", dtype);
+  MIT_CHECK_ARG(head_dim_ok(Dh), "mit_attention_plan: head_dim %ld unsupported (16, 32, 64, 128)", Dh);
+  MIT_CHECK_ARG(B > 0 && H > 0 && Lq > 0 && Lk > 0, "mit_attention_plan: empty problem");
+  const FwdPlan f = plan_fwd(dtype, B, H, Lq, Lk, Dh, x);
+  MIT_CHECK_ARG(f.family != PLAN_SPAN, "mit_attention_plan: K/V span >= 2 GiB");
+  const bool head = f.family == MIT_ATTN_FWD_HEAD || f.family == MIT_ATTN_FWD_HEAD_DROP;
+  *out = mit_attn_plan{f.family, head ? f.nw : 0, head ? f.lkp : 0, -1, 0, 0};
+  if (gg) {
+    const BwdPlan b = plan_bwd(dtype, B, H, Lq, Lk, Dh, x, gg);
+    MIT_CHECK_ARG(b.family != PLAN_SPAN, "mit_attention_plan: operand span >= 2 GiB");
+    out->bwd = b.family;
+    out->bwd_nw = b.family == MIT_ATTN_BWD_HEAD ? HB_NT / 64 : 0;
+    out->bwd_lkp = b.family == MIT_ATTN_BWD_HEAD ? b.lkp : 0;
+  }
+  return MIT_OK;
+}
+
 extern "C" int mit_attention_fwd(int dtype, long B, long H, long Lq, long Lk, long Dh, const mit_attn_args* x,
                                  void* stream) {
   MIT_CHECK_ARG(x && x->q && x->k && x->v && x->o, "mit_attention_fwd: null pointer");
@@ -1213,53 +1323,26 @@ extern "C" int mit_attention_fwd(int dtype, long B, long H, long Lq, long Lk, lo
   AttnK a = make_k(x);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((Lq + 63) / 64), (unsigned)H, (unsigned)B);
-  // the MFMA kernels are written for head_dim 64 (every ViT / CLIP tower and the 512/768-wide
-  // decoders); other head dims run the generic kernels
-  const bool mfma_ok = Dh == D && dtype == MIT_BF16 && x->q_row % 8 == 0 && x->q_batch % 8 == 0 && x->k_row % 8 == 0 &&
-                       x->k_batch % 8 == 0 && x->v_row % 8 == 0 && x->v_batch % 8 == 0 && x->o_row % 4 == 0 &&
-                       x->o_batch % 4 == 0 && ((uintptr_t)x->q | (uintptr_t)x->k | (uintptr_t)x->v) % 16 == 0 &&
-                       ((uintptr_t)x->o % 8) == 0;
-  if (mfma_ok) {
-    const long kb = 2 * ((Lk - 1) * x->k_row + D), vb = 2 * ((Lk - 1) * x->v_row + D);
-    MIT_CHECK_ARG(kb < (1L << 31) && vb < (1L << 31), "mit_attention_fwd: K/V span >= 2 GiB");
-    if (!a.causal && !a.tok && Lk <= HK_MAX && H <= 65535 && B <= 65535 &&
-        (!a.dropout || (double)B * (double)H * (double)Lq * (double)Lk < g_idx32_limit)) {
-      // head-resident K/V: one workgroup per (b, h), NW waves balanced over the 16-query tiles.
-      // K/V rows are staged to a multiple of 16 (the key tail of < 64 runs 16-key tiles: a ViT-B/16
-      // head of 197 keys sweeps 208 instead of 256; 28.5 -> 27.7 us, tools/attn_bench.py). <= 8 waves
-      // whenever two heads fit the LDS, so a CU holds two workgroups and one stages its K/V while the
-      // other computes. Three 5-wave workgroups per CU (one round of the 768 heads instead of 1.5,
-      // 52 KiB each) measured slower (30.8 us): the CU's VALU, not the rounds, bounds this kernel.
-      // The dropout instance is built for <= 512 threads.
-      constexpr int pad = 16;
-      const int lkp = (int)((Lk + pad - 1) / pad * pad);
-      const int nqt = (int)((Lq + 15) / 16);
-      const int maxw = (a.dropout || 2 * lkp * 256 <= 160 * 1024) ? 8 : 16;
-      // every wave the occupancy allows, the query tiles' rounds unbalanced (CLIP-L/14@336: 37 = 16 + 16 + 5
-      // in one workgroup per CU; ViT-B/16: 13 = 8 + 5 in two) rather than fewer balanced waves (13 + 13 + 11,
-      // 7 + 6): more waves to hide the sweep's latency, 47.2 -> 45.2 / 26.7 -> 26.5 us, configs[2]
-      // 2067 -> 2078 pairs/s (profiles/r05_decoder_experiments.txt)
-      const int nw = std::min(nqt, maxw);
-      const int lds = lkp * 256;
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void*)attn_fwd_head<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  HK_MAX * 256);
-        (void)hipFuncSetAttribute((const void*)attn_fwd_head<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  HK_MAX * 256);
-        attr = true;
-      }
-      dim3 hg((unsigned)H, (unsigned)B);
-      if (a.dropout)
-        hipLaunchKernelGGL(attn_fwd_head<true>, hg, dim3(64 * nw), lds, s, H, Lq, Lk, a, (int)kb, (int)vb, lkp);
-      else
-        hipLaunchKernelGGL(attn_fwd_head<false>, hg, dim3(64 * nw), lds, s, H, Lq, Lk, a, (int)kb, (int)vb, lkp);
-    } else if (!a.dropout || (double)B * (double)H * (double)Lq * (double)Lk < g_idx32_limit) {
-      hipLaunchKernelGGL(attn_fwd_mfma, grid, dim3(256), 0, s, H, Lq, Lk, a, (int)kb, (int)vb);
-    } else {  // dropout indices past 2^32 (the MFMA kernels form them in 32 bits)
-      hipLaunchKernelGGL((attn_fwd_simple<bf16, 64>), grid, dim3(64), 0, s, H, Lq, Lk, a);
+  const FwdPlan p = plan_fwd(dtype, B, H, Lq, Lk, Dh, x);
+  MIT_CHECK_ARG(p.family != PLAN_SPAN, "mit_attention_fwd: K/V span >= 2 GiB");
+  if (p.family == MIT_ATTN_FWD_HEAD || p.family == MIT_ATTN_FWD_HEAD_DROP) {
+    const int lds = p.lkp * 256;
+    static bool attr = false;
+    if (!attr) {
+      (void)hipFuncSetAttribute((const void*)attn_fwd_head<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                HK_MAX * 256);
+      (void)hipFuncSetAttribute((const void*)attn_fwd_head<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                HK_MAX * 256);
+      attr = true;
     }
-  } else if (dtype == MIT_BF16) {
+    dim3 hg((unsigned)H, (unsigned)B);
+    if (p.family == MIT_ATTN_FWD_HEAD_DROP)
+      hipLaunchKernelGGL(attn_fwd_head<true>, hg, dim3(64 * p.nw), lds, s, H, Lq, Lk, a, (int)p.kb, (int)p.vb, p.lkp);
+    else
+      hipLaunchKernelGGL(attn_fwd_head<false>, hg, dim3(64 * p.nw), lds, s, H, Lq, Lk, a, (int)p.kb, (int)p.vb, p.lkp);
+  } else if (p.family == MIT_ATTN_FWD_MFMA) {
+    hipLaunchKernelGGL(attn_fwd_mfma, grid, dim3(256), 0, s, H, Lq, Lk, a, (int)p.kb, (int)p.vb);
+  } else if (dtype == MIT_BF16) {  // also head_dim 64 whose dropout indices pass 2^32 (the MFMA kernels form them in 32 bits)
     DISPATCH_DH(Dh, hipLaunchKernelGGL((attn_fwd_simple<bf16, DH>), grid, dim3(64), 0, s, H, Lq, Lk, a));
   } else {
     DISPATCH_DH(Dh, hipLaunchKernelGGL((attn_fwd_simple<float, DH>), grid, dim3(64), 0, s, H, Lq, Lk, a));
@@ -1285,39 +1368,20 @@ extern "C" int mit_attention_bwd(int dtype, long B, long H, long Lq, long Lk, lo
   hipStream_t s = (hipStream_t)stream;
   dim3 gq((unsigned)((Lq + 63) / 64), (unsigned)H, (unsigned)B);
   dim3 gk((unsigned)((Lk + 63) / 64), (unsigned)H, (unsigned)B);
-  auto al = [](const void* p, int n) { return ((uintptr_t)p % n) == 0; };
-  const bool mfma_ok = Dh == D && dtype == MIT_BF16 && x->q_row % 8 == 0 && x->q_batch % 8 == 0 && x->k_row % 8 == 0 &&
-                       x->k_batch % 8 == 0 && x->v_row % 8 == 0 && x->v_batch % 8 == 0 && x->o_row % 8 == 0 &&
-                       x->o_batch % 8 == 0 && gg->do_row % 8 == 0 && gg->do_batch % 8 == 0 && gg->dq_row % 4 == 0 &&
-                       gg->dq_batch % 4 == 0 && gg->dk_row % 4 == 0 && gg->dk_batch % 4 == 0 && gg->dv_row % 4 == 0 &&
-                       gg->dv_batch % 4 == 0 && al(x->q, 16) && al(x->k, 16) && al(x->v, 16) && al(x->o, 16) &&
-                       al(gg->dout, 16) && al(gg->dq, 8) && al(gg->dk, 8) && al(gg->dv, 8);
-  if (mfma_ok) {
-    AttnBwdBytes nb;
-    const long qb = 2 * ((Lq - 1) * x->q_row + D), kb = 2 * ((Lk - 1) * x->k_row + D);
-    const long vb = 2 * ((Lk - 1) * x->v_row + D), db = 2 * ((Lq - 1) * gg->do_row + D);
-    MIT_CHECK_ARG(qb < (1L << 31) && kb < (1L << 31) && vb < (1L << 31) && db < (1L << 31),
-                  "mit_attention_bwd: operand span >= 2 GiB");
-    nb.q = (int)qb;
-    nb.k = (int)kb;
-    nb.v = (int)vb;
-    nb.dO = (int)db;
-    // (the head kernel forms its dropout indices in 32 bits: B * H * Lq * Lk < 2^32)
-    if (Lq <= 64 && Lk <= HB_MAXK && H <= 65535 && B <= 65535 && x->o_row % 8 == 0 &&
-        (double)B * (double)H * (double)Lq * (double)Lk < g_idx32_limit) {
-      const int lkp = (int)((Lk + 31) / 32 * 32);
-      const int lds = 2 * lkp * 128 + 2 * 64 * 128 + 2 * 64 * 4;
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd_head, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  2 * HB_MAXK * 128 + 2 * 64 * 128 + 2 * 64 * 4);
-        attr = true;
-      }
-      hipLaunchKernelGGL(attn_bwd_head, dim3((unsigned)H, (unsigned)B), dim3(HB_NT), lds, s, H, Lq, Lk, a, g, nb, lkp);
-    } else {
-      hipLaunchKernelGGL(attn_bwd_dq_mfma, gq, dim3(256), 0, s, H, Lq, Lk, a, g, nb);
-      hipLaunchKernelGGL(attn_bwd_dkv_mfma, gk, dim3(256), 0, s, H, Lq, Lk, a, g, nb);
+  const BwdPlan p = plan_bwd(dtype, B, H, Lq, Lk, Dh, x, gg);
+  MIT_CHECK_ARG(p.family != PLAN_SPAN, "mit_attention_bwd: operand span >= 2 GiB");
+  if (p.family == MIT_ATTN_BWD_HEAD) {
+    const int lds = 2 * p.lkp * 128 + 2 * 64 * 128 + 2 * 64 * 4;
+    static bool attr = false;
+    if (!attr) {
+      (void)hipFuncSetAttribute((const void*)attn_bwd_head, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                2 * HB_MAXK * 128 + 2 * 64 * 128 + 2 * 64 * 4);
+      attr = true;
     }
+    hipLaunchKernelGGL(attn_bwd_head, dim3((unsigned)H, (unsigned)B), dim3(HB_NT), lds, s, H, Lq, Lk, a, g, p.nb, p.lkp);
+  } else if (p.family == MIT_ATTN_BWD_MFMA) {
+    hipLaunchKernelGGL(attn_bwd_dq_mfma, gq, dim3(256), 0, s, H, Lq, Lk, a, g, p.nb);
+    hipLaunchKernelGGL(attn_bwd_dkv_mfma, gk, dim3(256), 0, s, H, Lq, Lk, a, g, p.nb);
   } else if (dtype == MIT_BF16) {
     DISPATCH_DH(Dh, hipLaunchKernelGGL((attn_bwd_dq_simple<bf16, DH>), gq, dim3(64), 0, s, H, Lq, Lk, a, g);
                     hipLaunchKernelGGL((attn_bwd_dkv_simple<bf16, DH>), gk, dim3(64), 0, s, H, Lq, Lk, a, g));

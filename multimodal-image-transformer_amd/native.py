@@ -83,6 +83,15 @@ class AttnGrads(ctypes.Structure):
                 ("delta_ws", vp)]
 
 
+class AttnPlan(ctypes.Structure):
+    _fields_ = [("fwd", I), ("fwd_nw", I), ("fwd_lkp", I), ("bwd", I), ("bwd_nw", I), ("bwd_lkp", I)]
+
+
+# mit_attn_plan.fwd / .bwd
+ATTN_GENERIC, ATTN_FWD_MFMA, ATTN_FWD_HEAD, ATTN_FWD_HEAD_DROP = 0, 1, 2, 3
+ATTN_BWD_MFMA, ATTN_BWD_HEAD = 1, 2
+
+
 # name -> (restype, argtypes); mirrors include/mit_hip.h one to one
 SIGNATURES = {
     "mit_last_error": (ctypes.c_char_p, []),
@@ -103,6 +112,8 @@ SIGNATURES = {
     "mit_attention_fwd": (I, [I, L, L, L, L, L, ctypes.POINTER(AttnArgs), vp]),
     "mit_attention_bwd": (I, [I, L, L, L, L, L, ctypes.POINTER(AttnArgs), ctypes.POINTER(AttnGrads), vp]),
     "mit_attention_set_index_limit": (I, [ctypes.c_double]),
+    "mit_attention_plan": (I, [I, L, L, L, L, L, ctypes.POINTER(AttnArgs), ctypes.POINTER(AttnGrads),
+                               ctypes.POINTER(AttnPlan)]),
     "mit_im2col": (I, [I, L, L, L, L, L, vp, vp, L, vp]),
     "mit_vit_assemble": (I, [I, L, L, L, vp, vp, vp, vp, vp]),
     "mit_embed_fwd": (I, [I, L, L, L, vp, vp, Fl, vp, Fl, vp, U32, vp, vp]),
@@ -619,6 +630,16 @@ def attention_fwd(dtype, B, H, Lq, Lk, args: AttnArgs, Dh=64):
 def attention_bwd(dtype, B, H, Lq, Lk, args: AttnArgs, grads: AttnGrads, Dh=64):
     _check(lib().mit_attention_bwd(dtype, B, H, Lq, Lk, Dh, ctypes.byref(args), ctypes.byref(grads), stream_ptr()),
            "mit_attention_bwd")
+
+
+def attention_plan(dtype, B, H, Lq, Lk, args: AttnArgs, grads: AttnGrads = None, Dh=64) -> AttnPlan:
+    """The kernels attention_fwd / attention_bwd would launch for these arguments (mit_attention_plan: host
+    only, no GPU needed). grads = None: the backward is not planned (bwd = -1)."""
+    out = AttnPlan()
+    _check(lib().mit_attention_plan(dtype, B, H, Lq, Lk, Dh, ctypes.byref(args),
+                                    ctypes.byref(grads) if grads is not None else None, ctypes.byref(out)),
+           "mit_attention_plan")
+    return out
 
 
 def attn_grads(dout, do_row, do_batch, dq, dq_row, dq_batch, dk, dk_row, dk_batch, dv, dv_row, dv_batch, delta_ws):

@@ -233,12 +233,13 @@ def test_attention_fwd_bwd(dtype, D, kind):
         Lq, Lk = 63, 230
     elif kind == "cross_drop40":
         Lq, Lk = 63, 40
-    # the two-pass head kernel (attn_fwd_head2p, <= 256 keys): 16 full tiles; one ragged tile with dropout
+    # attn_fwd_head with whole 64-key chunks only (256 keys, no tail); 17 keys: no whole chunk, a 32-row tail, with dropout
     elif kind == "cross256":
         Lq, Lk = 50, 256
     elif kind == "cross_drop17":
         Lq, Lk = 63, 17
-    # two query tiles over 5 key units (4 chunks + a 48-key tail): the head kernel's key split in 4 parts
+    # two query tiles (two waves), each sweeping 4 chunks + a 48-key tail (attn_fwd_head has no key split: a wave
+    # owns its query tile's whole key range)
     elif kind in ("cross_q20", "cross_q20_drop"):
         Lq, Lk = 20, 300
     else:
