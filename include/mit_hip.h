@@ -167,8 +167,11 @@ int mit_gemm_grouped(const mit_gemm_args* args, int n, const mit_ln_grads_job* l
  * Replaces nn.LayerNorm in tf/models/vit/modeling_vit.py:274,281,385 (pre-LN, eps 1e-12),
  * tf/models/clip/modeling_clip.py:358,360,642 (eps 1e-5) and the post-LN residual blocks of
  * torch/nn/modules/transformer.py:1144-1153: y = LN(x + dropout(r)).
- *   r may be NULL (plain LN). z (may be NULL) receives x + dropout(r) (saved for the backward).
- *   mean/rstd (f32 [rows], may be NULL) saved for the backward. gamma/beta f32 [cols]. */
+ *   r may be NULL (plain LN; r_drop_p is then ignored). z (may be NULL) receives x + dropout(r) (saved for the
+ *   backward). x, r and y are [rows, cols] windows of row stride ldx / ldr / ldy (>= cols; ldr is ignored when
+ *   r is NULL); z is [rows, cols] DENSE (row stride cols, whatever ldy is), as the backward reads it.
+ *   dropout index = row * cols + col. mean/rstd (f32 [rows], may be NULL) saved for the backward.
+ *   gamma/beta f32 [cols]. cols <= 2048. Any alignment is accepted; mit_layernorm_plan tells which kernel runs. */
 int mit_layernorm_fwd(int dtype, long rows, long cols, const void* x, long ldx, const void* r, long ldr,
                       float r_drop_p, const uint64_t* seed, uint32_t site, const float* gamma, const float* beta,
                       float eps, void* z, void* y, long ldy, float* mean, float* rstd, void* stream);
@@ -189,6 +192,7 @@ int mit_residual_out(long rows, long cols, const float* x, long ldx, const void*
 
 /* Backward of y = LN(z), z = x + dropout(r):
  *   dx = dz = dLN(dy) (dx may alias dy), dr = dz * dropout_mask (may be NULL)
+ *   dy, z, dx and dr are [rows, cols] DENSE (row stride cols): z is what mit_layernorm_fwd wrote.
  *   dgamma/dbeta: f32 [cols], overwritten. Both NULL: the per-block column partials are left in
  *     ws and mit_layernorm_param_grads reduces them later (e.g. on another stream, off the dX chain).
  *   ws: f32 workspace of >= mit_layernorm_bwd_ws_floats(rows, cols) floats. */
@@ -197,6 +201,29 @@ int mit_layernorm_bwd(int dtype, long rows, long cols, const void* dy, const voi
                       const float* rstd, const float* gamma, void* dx, void* dr, float r_drop_p, const uint64_t* seed,
                       uint32_t site, float* dgamma, float* dbeta, float* ws, void* stream);
 int mit_layernorm_param_grads(long rows, long cols, const float* ws, float* dgamma, float* dbeta, void* stream);
+/* The launches mit_layernorm_fwd / mit_layernorm_bwd would make for these arguments (no launch, nothing
+ * dereferenced: runs without a GPU). Both entry points and this one call the same two host decision functions
+ * (csrc/norm.hip plan_fwd / plan_bwd).
+ *   fwd (x != NULL; -1 when x is NULL), from x / ldx / r / ldr / z / y / ldy / gamma / beta as mit_layernorm_fwd takes them:
+ *     MIT_LN_PAIR (ln_fwd_pair_kernel, two rows per wave: bf16, cols 256, or 768 with r) and
+ *     MIT_LN_WIDE (ln_fwd_wide_kernel, 16 B per lane: bf16, cols % 8 == 0, cols <= 1024) need ldx, ldy (and ldr)
+ *       % 8 == 0 and x, y, r, z, gamma, beta 16-B aligned;
+ *     MIT_LN_VEC4 (ln_fwd_kernel<.., true>, 4 elements per lane: cols % 256 == 0, leading dims % 4 == 0, x, y, r, z
+ *       aligned to 4 elements, gamma and beta to 16 B);
+ *     MIT_LN_SCALAR (ln_fwd_kernel<.., false>): everything else.
+ *   bwd (dy != NULL; -1 when dy is NULL), from dy / z / dx / dr / gamma as mit_layernorm_bwd takes them:
+ *     MIT_LN_WIDE (ln_bwd_wide_kernel: bf16, cols % 8 == 0, cols <= 1024, all five 16-B aligned), MIT_LN_VEC4
+ *     (ln_bwd_kernel<.., true>: cols % 256 == 0, 4-element alignment, gamma 16 B), MIT_LN_SCALAR.
+ *   fwd_nv / bwd_nv: the NV template argument of the kernel (passes over the row: wide 1 for cols <= 512 else 2;
+ *     pair 1 / 3; vec4 and scalar ceil(cols / 256) resp. ceil(cols / 64) rounded up to 1, 2, 3, 4, 8, 16, 32).
+ * For tests that must know which kernel a shape ran, and for tools that attribute kernel time. */
+enum { MIT_LN_SCALAR = 0, MIT_LN_VEC4 = 1, MIT_LN_WIDE = 2, MIT_LN_PAIR = 3 };
+typedef struct {
+  int fwd, fwd_nv, bwd, bwd_nv;
+} mit_ln_plan;
+int mit_layernorm_plan(int dtype, long rows, long cols, const void* x, long ldx, const void* r, long ldr, const void* z,
+                       const void* y, long ldy, const float* gamma, const float* beta, const void* dy, const void* dx,
+                       const void* dr, mit_ln_plan* plan);
 /* Per-64-column (mean, M2) of each bf16 row: out[r][c / 64] = (mean, sum of squared deviations) over
  * columns c .. c + 63 (cols % 64 == 0): the ln_stats of a LayerNorm-folded GEMM (mit_gemm) whose input
  * rows no producer GEMM annotated (the encoder's embeddings). Replaces the statistics half of

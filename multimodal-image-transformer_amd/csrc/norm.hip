@@ -375,17 +375,23 @@ __global__ __launch_bounds__(256) void ln_param_reduce(long nblk, long cols, con
   }
 }
 
-template <typename T, bool VEC, typename F>
-void dispatch_nv(long cols, F&& f) {
-  const long per = VEC ? 256 : 64;
+// the NV instance of ln_fwd_kernel / ln_bwd_kernel for a width: 64 (scalar) or 256 (VEC) columns per (lane, i) pass
+static int ln_nv(long cols, bool vec) {
+  const long per = vec ? 256 : 64;
   const long nv = (cols + per - 1) / per;
-  if (nv <= 1) f(std::integral_constant<int, 1>());
-  else if (nv <= 2) f(std::integral_constant<int, 2>());
-  else if (nv <= 3) f(std::integral_constant<int, 3>());
-  else if (nv <= 4) f(std::integral_constant<int, 4>());
-  else if (nv <= 8) f(std::integral_constant<int, 8>());
-  else if (nv <= 16) f(std::integral_constant<int, 16>());
-  else f(std::integral_constant<int, 32>());
+  return nv <= 4 ? (int)nv : nv <= 8 ? 8 : nv <= 16 ? 16 : 32;
+}
+template <typename F>
+void dispatch_nv(int nv, F&& f) {
+  switch (nv) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 8: f(std::integral_constant<int, 8>()); break;
+    case 16: f(std::integral_constant<int, 16>()); break;
+    default: f(std::integral_constant<int, 32>()); break;
+  }
 }
 // bf16 rows with cols % 8 == 0, cols <= 1024 (every production width: 128 .. 1024): 16-B loads and
 // stores (8 columns per lane per 512-column pass) and RW rows per wave, all their loads issued before
@@ -599,6 +605,52 @@ __global__ __launch_bounds__(256) void ln_fwd_pair_kernel(long rows, long cols, 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dispatch: which kernel a call runs, decided from the dtype, the width, the leading dimensions and the
+// pointers' alignment alone. mit_layernorm_fwd / mit_layernorm_bwd launch what these two functions return
+// and mit_layernorm_plan reports it; none of them dereferences an operand here.
+// ------------------------------------------------------------------------------------------------
+struct LnPlan {
+  int family;  // MIT_LN_*
+  int nv;      // the NV template argument
+};
+
+static bool al(const void* p, size_t n) { return ((uintptr_t)p % n) == 0; }
+
+static LnPlan plan_fwd(int dtype, long cols, const void* x, long ldx, const void* r, long ldr, const void* z,
+                       const void* y, long ldy, const float* gamma, const float* beta) {
+  // bf16 rows with cols % 8 == 0, cols <= 1024 (every production width), 16-B rows: the 16-B-per-lane kernels
+  if (dtype == MIT_BF16 && cols % 8 == 0 && cols <= 1024 && ldx % 8 == 0 && ldy % 8 == 0 && (!r || ldr % 8 == 0) &&
+      al(x, 16) && al(y, 16) && al(r, 16) && al(z, 16) && al(gamma, 16) && al(beta, 16)) {
+    // widths whose two rows fill whole 64-lane passes (256: 1 pass, 768: 3): two rows per wave. Alone
+    // (tools/ln_bench.py, interleaved): 16384 x 256 6.1 vs 7.6-8.2 us, 12608 x 768 + residual + dropout
+    // (configs[3]'s decoder width) 18.3 vs 19.7-20.0 us; the encoder's 768-wide LayerNorm without residual is
+    // not faster (10.0 vs 9.9 us: x -> y alone copies in 6.2 us, the rest is per-row latency) and keeps the
+    // one-row form
+    if (cols == 256) return {MIT_LN_PAIR, 1};
+    if (cols == 768 && r) return {MIT_LN_PAIR, 3};
+    // one row per wave (2 / 4 rows per wave alone, tools/ln_bench.py: encoder 12608 x 768 9.4 vs
+    // 10.2 / 11.6 us, CLIP-L 36928 x 1024 24.7 vs 26.9 / 29.7 us, decoder 4032 x 512 + residual +
+    // dropout 6.3 vs 6.5 / 8.7 us): the most waves in flight
+    return {MIT_LN_WIDE, cols <= 512 ? 1 : 2};
+  }
+  const size_t esz = dtype == MIT_BF16 ? 2 : 4;
+  const bool vec = cols % 256 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (!r || ldr % 4 == 0) && al(x, 4 * esz) &&
+                   al(y, 4 * esz) && al(r, 4 * esz) && al(z, 4 * esz) && al(gamma, 16) && al(beta, 16);
+  return {vec ? MIT_LN_VEC4 : MIT_LN_SCALAR, ln_nv(cols, vec)};
+}
+
+static LnPlan plan_bwd(int dtype, long cols, const void* dy, const void* z, const void* dx, const void* dr,
+                       const float* gamma) {
+  if (dtype == MIT_BF16 && cols % 8 == 0 && cols <= 1024 && al(dy, 16) && al(z, 16) && al(dx, 16) && al(dr, 16) &&
+      al(gamma, 16))
+    return {MIT_LN_WIDE, cols <= 512 ? 1 : 2};
+  const size_t esz = dtype == MIT_BF16 ? 2 : 4;
+  const bool vec = cols % 256 == 0 && al(dy, 4 * esz) && al(z, 4 * esz) && al(dx, 4 * esz) && al(dr, 4 * esz) &&
+                   al(gamma, 16);
+  return {vec ? MIT_LN_VEC4 : MIT_LN_SCALAR, ln_nv(cols, vec)};
+}
+
 }  // namespace
 
 extern "C" int mit_layernorm_fwd(int dtype, long rows, long cols, const void* x, long ldx, const void* r, long ldr,
@@ -613,24 +665,12 @@ extern "C" int mit_layernorm_fwd(int dtype, long rows, long cols, const void* x,
   const int dropout = (r != nullptr) && r_drop_p > 0.f;
   const uint32_t th = drop_threshold(r_drop_p);
   const float sc = r_drop_p < 1.f ? 1.f / (1.f - r_drop_p) : 0.f;
-  const size_t esz = dtype == MIT_BF16 ? 2 : 4;
-  const bool vec = cols % 256 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (!r || ldr % 4 == 0) &&
-                   ((uintptr_t)x % (4 * esz)) == 0 && ((uintptr_t)y % (4 * esz)) == 0 &&
-                   (!r || ((uintptr_t)r % (4 * esz)) == 0) && (!z || ((uintptr_t)z % (4 * esz)) == 0) &&
-                   ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0;
+  const LnPlan p = plan_fwd(dtype, cols, x, ldx, r, ldr, z, y, ldy, gamma, beta);
+  const bool vec = p.family == MIT_LN_VEC4;
   dim3 grid((unsigned)((rows + 3) / 4));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == MIT_BF16 && cols % 8 == 0 && cols <= 1024 && ldx % 8 == 0 && ldy % 8 == 0 &&
-      (!r || ldr % 8 == 0) && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)r | (uintptr_t)z) % 16) == 0 &&
-      ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0) {
-    // one row per wave (2 / 4 rows per wave alone, tools/ln_bench.py: encoder 12608 x 768 9.4 vs
-    // 10.2 / 11.6 us, CLIP-L 36928 x 1024 24.7 vs 26.9 / 29.7 us, decoder 4032 x 512 + residual +
-    // dropout 6.3 vs 6.5 / 8.7 us): the most waves in flight
-    // widths whose two rows fill whole 64-lane passes (256: 1 pass, 768: 3): two rows per wave. Alone (tools/ln_bench.py, interleaved): 16384 x 256
-    // 6.1 vs 7.6-8.2 us, 12608 x 768 + residual + dropout (configs[3]'s decoder width) 18.3 vs
-    // 19.7-20.0 us; the encoder's 768-wide LayerNorm without residual is not faster (10.0 vs 9.9 us:
-    // x -> y alone copies in 6.2 us, the rest is per-row latency) and keeps the one-row form
-    if ((cols == 256 || (cols == 768 && r))) {
+  if (p.family == MIT_LN_PAIR || p.family == MIT_LN_WIDE) {
+    if (p.family == MIT_LN_PAIR) {
       const dim3 g2((unsigned)((rows + 7) / 8));
       auto go = [&](auto nvc) {
         constexpr int NVc = decltype(nvc)::value;
@@ -643,7 +683,7 @@ extern "C" int mit_layernorm_fwd(int dtype, long rows, long cols, const void* x,
                              (const bf16*)r, ldr, seed, site, th, sc, dropout, gamma, beta, eps, (bf16*)z, (bf16*)y,
                              ldy, mean, rstd);
       };
-      if (cols == 256) go(std::integral_constant<int, 1>());
+      if (p.nv == 1) go(std::integral_constant<int, 1>());
       else go(std::integral_constant<int, 3>());
       MIT_LAUNCH_CHECK("mit_layernorm_fwd");
       return MIT_OK;
@@ -661,7 +701,7 @@ extern "C" int mit_layernorm_fwd(int dtype, long rows, long cols, const void* x,
                            mean, rstd);
     };
     auto by_rw = [&](auto nvc) { launch(nvc, std::integral_constant<int, 1>()); };
-    if (cols <= 512) by_rw(std::integral_constant<int, 1>());
+    if (p.nv == 1) by_rw(std::integral_constant<int, 1>());
     else by_rw(std::integral_constant<int, 2>());
     MIT_LAUNCH_CHECK("mit_layernorm_fwd");
     return MIT_OK;
@@ -669,7 +709,7 @@ extern "C" int mit_layernorm_fwd(int dtype, long rows, long cols, const void* x,
   auto go = [&](auto tt, auto vv) {
     typedef decltype(tt) T;
     constexpr bool V = decltype(vv)::value;
-    dispatch_nv<T, V>(cols, [&](auto nv) {
+    dispatch_nv(p.nv, [&](auto nv) {
       constexpr int NV = decltype(nv)::value;
       hipLaunchKernelGGL((ln_fwd_kernel<T, NV, V>), grid, dim3(256), 0, s, rows, cols, (const T*)x, ldx, (const T*)r,
                          ldr, seed, site, th, sc, dropout, gamma, beta, eps, (T*)z, (T*)y, ldy, mean, rstd);
@@ -781,23 +821,20 @@ extern "C" int mit_layernorm_bwd(int dtype, long rows, long cols, const void* dy
   const uint32_t th = drop_threshold(r_drop_p);
   const float sc = r_drop_p < 1.f ? 1.f / (1.f - r_drop_p) : 0.f;
   const long nblk = (rows + BWD_ROWS - 1) / BWD_ROWS;
-  const size_t esz = dtype == MIT_BF16 ? 2 : 4;
-  const bool vec = cols % 256 == 0 && ((uintptr_t)dy % (4 * esz)) == 0 && ((uintptr_t)z % (4 * esz)) == 0 &&
-                   ((uintptr_t)dx % (4 * esz)) == 0 && (!dr || ((uintptr_t)dr % (4 * esz)) == 0) &&
-                   ((uintptr_t)gamma % 16) == 0;
+  const LnPlan p = plan_bwd(dtype, cols, dy, z, dx, dr, gamma);
+  const bool vec = p.family == MIT_LN_VEC4;
   hipStream_t s = (hipStream_t)stream;
   auto go = [&](auto tt, auto vv) {
     typedef decltype(tt) T;
     constexpr bool V = decltype(vv)::value;
-    dispatch_nv<T, V>(cols, [&](auto nv) {
+    dispatch_nv(p.nv, [&](auto nv) {
       constexpr int NV = decltype(nv)::value;
       hipLaunchKernelGGL((ln_bwd_kernel<T, NV, V>), dim3((unsigned)nblk), dim3(256), 0, s, rows, cols, (const T*)dy,
                          (const T*)z, mean, rstd, gamma, (T*)dx, (T*)dr, seed, site, th, sc, dropout, ws);
     });
   };
-  if (dtype == MIT_BF16 && cols % 8 == 0 && cols <= 1024 &&
-      (((uintptr_t)dy | (uintptr_t)z | (uintptr_t)dx | (uintptr_t)dr | (uintptr_t)gamma) % 16) == 0) {
-    if (cols <= 512)
+  if (p.family == MIT_LN_WIDE) {
+    if (p.nv == 1)
       hipLaunchKernelGGL((ln_bwd_wide_kernel<1>), dim3((unsigned)nblk), dim3(256), 0, s, rows, cols, (const bf16*)dy,
                          (const bf16*)z, mean, rstd, gamma, (bf16*)dx, (bf16*)dr, seed, site, th, sc, dropout, ws);
     else
@@ -828,6 +865,31 @@ extern "C" int mit_layernorm_param_grads(long rows, long cols, const float* ws, 
   hipLaunchKernelGGL(ln_param_reduce, dim3((unsigned)((2 * cols + 15) / 16)), dim3(256), 0, (hipStream_t)stream, nblk,
                      cols, ws, dgamma, dbeta);
   MIT_LAUNCH_CHECK("mit_layernorm_param_grads");
+  return MIT_OK;
+}
+
+extern "C" int mit_layernorm_plan(int dtype, long rows, long cols, const void* x, long ldx, const void* r, long ldr,
+                                  const void* z, const void* y, long ldy, const float* gamma, const float* beta,
+                                  const void* dy, const void* dx, const void* dr, mit_ln_plan* plan) {
+  MIT_CHECK_ARG(plan, "mit_layernorm_plan: null pointer");
+  MIT_CHECK_ARG(dtype == MIT_BF16 || dtype == MIT_F32, "mit_layernorm_plan: bad dtype %d", dtype);
+  MIT_CHECK_ARG(rows > 0, "mit_layernorm_plan: empty problem");
+  MIT_CHECK_ARG(cols > 0 && cols <= 64 * MAXV_ALL, "mit_layernorm_plan: cols %ld out of range", cols);
+  MIT_CHECK_ARG(x || dy, "mit_layernorm_plan: neither a forward (x) nor a backward (dy) is given");
+  *plan = mit_ln_plan{-1, 0, -1, 0};
+  if (x) {
+    MIT_CHECK_ARG(y && gamma && beta, "mit_layernorm_plan: null pointer");
+    MIT_CHECK_ARG(ldx >= cols && ldy >= cols && (!r || ldr >= cols), "mit_layernorm_plan: bad leading dim");
+    const LnPlan f = plan_fwd(dtype, cols, x, ldx, r, ldr, z, y, ldy, gamma, beta);
+    plan->fwd = f.family;
+    plan->fwd_nv = f.nv;
+  }
+  if (dy) {
+    MIT_CHECK_ARG(z && dx && gamma, "mit_layernorm_plan: null pointer");
+    const LnPlan b = plan_bwd(dtype, cols, dy, z, dx, dr, gamma);
+    plan->bwd = b.family;
+    plan->bwd_nv = b.nv;
+  }
   return MIT_OK;
 }
 

@@ -27,7 +27,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MIT_HIP_LIB", os.path.join(_HERE, "lib", "libmit_hip.so"))
-ABI_VERSION = 6  # mit_abi_version() of the library this binding matches (include/mit_hip.h)
+ABI_VERSION = 7  # mit_abi_version() of the library this binding matches (include/mit_hip.h)
 ARGMAX_SLOTS = 16  # MIT_ARGMAX_SLOTS: slots per row of the decode head's argmax keys
 
 F32, BF16 = 0, 1
@@ -92,6 +92,14 @@ ATTN_GENERIC, ATTN_FWD_MFMA, ATTN_FWD_HEAD, ATTN_FWD_HEAD_DROP = 0, 1, 2, 3
 ATTN_BWD_MFMA, ATTN_BWD_HEAD = 1, 2
 
 
+class LnPlan(ctypes.Structure):
+    _fields_ = [("fwd", I), ("fwd_nv", I), ("bwd", I), ("bwd_nv", I)]
+
+
+# mit_ln_plan.fwd / .bwd
+LN_SCALAR, LN_VEC4, LN_WIDE, LN_PAIR = 0, 1, 2, 3
+
+
 # name -> (restype, argtypes); mirrors include/mit_hip.h one to one
 SIGNATURES = {
     "mit_last_error": (ctypes.c_char_p, []),
@@ -109,6 +117,7 @@ SIGNATURES = {
     "mit_layernorm_bwd_ws_floats": (L, [L, L]),
     "mit_layernorm_bwd": (I, [I, L, L, vp, vp, vp, vp, vp, vp, vp, Fl, vp, U32, vp, vp, vp, vp]),
     "mit_layernorm_param_grads": (I, [L, L, vp, vp, vp, vp]),
+    "mit_layernorm_plan": (I, [I, L, L, vp, L, vp, L, vp, vp, L, vp, vp, vp, vp, vp, ctypes.POINTER(LnPlan)]),
     "mit_attention_fwd": (I, [I, L, L, L, L, L, ctypes.POINTER(AttnArgs), vp]),
     "mit_attention_bwd": (I, [I, L, L, L, L, L, ctypes.POINTER(AttnArgs), ctypes.POINTER(AttnGrads), vp]),
     "mit_attention_set_index_limit": (I, [ctypes.c_double]),
@@ -562,10 +571,12 @@ def linear(x, w, out, *, bias=None, act=ACT_NONE, residual=None, drop_p=0.0, see
 
 
 def layernorm_fwd(x, gamma, beta, eps, y, *, r=None, drop_p=0.0, seed=None, site=0, z=None, mean=None, rstd=None,
-                  rows=None, cols=None, ldx=None, ldy=None):
+                  rows=None, cols=None, ldx=None, ldr=None, ldy=None):
+    """y = LN(x + dropout(r)) (mit_layernorm_fwd). x / r / y: [rows, cols] windows of row stride ldx / ldr / ldy
+    (default cols); z (if given) is written dense."""
     cols = cols if cols is not None else x.shape[-1]
     rows = rows if rows is not None else x.numel() // cols
-    _check(lib().mit_layernorm_fwd(dtype_code(x), rows, cols, ptr(x), ldx or cols, ptr(r), cols, drop_p, ptr(seed),
+    _check(lib().mit_layernorm_fwd(dtype_code(x), rows, cols, ptr(x), ldx or cols, ptr(r), ldr or cols, drop_p, ptr(seed),
                                    site, ptr(gamma), ptr(beta), eps, ptr(z), ptr(y), ldy or cols, ptr(mean),
                                    ptr(rstd), stream_ptr()), "mit_layernorm_fwd")
 
@@ -615,6 +626,17 @@ def layernorm_bwd(dy, z, mean, rstd, gamma, dx, dgamma, dbeta, ws, *, dr=None, d
 def layernorm_param_grads(rows, cols, ws, dgamma, dbeta):
     _check(lib().mit_layernorm_param_grads(rows, cols, ptr(ws), ptr(dgamma), ptr(dbeta), stream_ptr()),
            "mit_layernorm_param_grads")
+
+
+def layernorm_plan(dtype, rows, cols, *, x=None, ldx=None, r=None, ldr=None, z=None, y=None, ldy=None, gamma=None,
+                   beta=None, dy=None, dx=None, dr=None) -> LnPlan:
+    """The kernels layernorm_fwd (x given) / layernorm_bwd (dy given) would launch for these arguments
+    (mit_layernorm_plan: host only, no GPU needed); fwd / bwd = -1 for the direction that is not given."""
+    out = LnPlan()
+    _check(lib().mit_layernorm_plan(dtype, rows, cols, ptr(x), ldx or cols, ptr(r), ldr or cols, ptr(z), ptr(y),
+                                    ldy or cols, ptr(gamma), ptr(beta), ptr(dy), ptr(dx), ptr(dr), ctypes.byref(out)),
+           "mit_layernorm_plan")
+    return out
 
 
 def attn_args(q, q_row, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_row, o_batch, *, lse=None,
