@@ -319,6 +319,19 @@ int mit_attention_plan(int dtype, long B, long H, long Lq, long Lk, long Dh, con
 int mit_im2col(int dtype, long B, long C, long H, long W, long P, const float* img, void* out, long kpad, void* stream);
 int mit_vit_assemble(int dtype, long B, long np, long E, const void* patch, const float* cls, const float* pos, void* h,
                      void* stream);
+/* The kernel the two entry points above would launch for these arguments (no launch, nothing dereferenced: runs
+ * without a GPU; the entry point and its query call the same host decision function, csrc/misc.hip), -1 for
+ * arguments the entry point rejects. Both results are exact in either family: a cast of the gathered pixel or +0
+ * in the padding columns; one f32 add, then the dtype's rounding.
+ *   im2col:   MIT_ELT_VEC8 (im2col8_kernel: 8 columns per thread, 32-bit indices) for bf16 with P % 8 == 0,
+ *             W % 4 == 0, kpad % 8 == 0, img and out 16-B aligned, B*np*kpad / 8 and B*C*H*W below 2^31;
+ *             MIT_ELT_SCALAR (im2col_kernel<T>) otherwise (f32; CLIP-L/14: P = 14).
+ *   assemble: MIT_ELT_VEC8 (assemble8_kernel) for bf16 with E % 8 == 0, patch / cls / pos / h 16-B aligned and
+ *             B*(np+1)*E / 8 below 2^31; MIT_ELT_SCALAR (assemble_kernel<T>) otherwise. */
+enum { MIT_ELT_SCALAR = 0, MIT_ELT_VEC8 = 1 };
+int mit_im2col_plan(int dtype, long B, long C, long H, long W, long P, const float* img, const void* out, long kpad);
+int mit_vit_assemble_plan(int dtype, long B, long np, long E, const void* patch, const float* cls, const float* pos,
+                          const void* h);
 
 /* ---------------------------------------------------------------------------------------------
  * Decoder input: x = dropout(Emb[tok] * scale + pe[t]) (decoder.py:168-171, 71-72).
@@ -330,9 +343,18 @@ int mit_embed_fwd(int dtype, long B, long T, long d, const int64_t* tokens, cons
  * plan != NULL: DETERMINISTIC — each token's row is the sum of its positions' rows in position order
  * (d % 8 == 0, B*T <= 16384); plan = int32 [mit_embed_plan_ints(B*T)] filled by mit_embed_plan from
  * the same tokens (one workgroup sorts (token, position); any time after the tokens are final).
- * plan == NULL: float atomics (order-dependent rounding). */
+ * plan == NULL: float atomics (order-dependent rounding).
+ * What is written: with a plan, the row of every token present among the positions and different from pad_idx is
+ * STORED (whatever dtable held), every other row -- absent tokens, pad_idx -- is left untouched; without a plan the
+ * rows are ADDED to. Token ids must be in [0, rows of dtable): anything else is undefined. The dropout index of
+ * element (b, t, c) is the flat (b*T + t)*d + c in both directions.
+ * The plan: plan[k] = the position of sorted slot k of the stable sort of the positions by token (equal tokens in
+ * ascending position), plan[n + k] = the length of the token's run that starts at slot k, 0 elsewhere.
+ * mit_embed_plan_keys_per_thread: the embed_plan_kernel<KPT> instance mit_embed_plan launches (host only): 1 for
+ * n <= 1024, 2 to 2048, 4 to 4096, 8 to 8192, 16 to 16384; 0 for n == 0 (no launch); -1 for a rejected n. */
 long mit_embed_plan_ints(long n);
 int mit_embed_plan(const int64_t* tokens, long n, int* plan, void* stream);
+int mit_embed_plan_keys_per_thread(long n);
 int mit_embed_bwd(int dtype, long B, long T, long d, const int64_t* tokens, const void* dx, float scale, float drop_p,
                   const uint64_t* seed, uint32_t site, int pad_idx, const int* plan, float* dtable, void* stream);
 
@@ -346,13 +368,27 @@ int mit_embed_bwd(int dtype, long B, long T, long d, const int64_t* tokens, cons
  *     row_loss (f32 [rows], may be NULL): scratch for a deterministic loss sum (per-row losses added
  *     in row order; bf16 rows with V <= 10240 also take the register-resident one-wave-per-row
  *     kernel). NULL: per-row float atomics into loss_sum (order-dependent rounding).
- * scalar_div: out[0] = a[0] / b[0] (mean loss = loss_sum / count, on device, no host sync). */
+ * scalar_div: out[0] = a[0] / b[0] (mean loss = loss_sum / count, on device, no host sync).
+ * Pinned by tests/misc_contract.py:
+ *   - targets must be in [0, V) or equal ignore_index; anything else is undefined;
+ *   - loss_sum and count are ADDED to, never overwritten; row_loss[r] is written for every row (0 when ignored);
+ *   - want_grad == 0 writes nothing to logits;
+ *   - columns >= V of a row: the wave-per-row kernel (MIT_CE_ROWS) writes columns V..round8(V) as 0 with
+ *     want_grad and nothing past round8(V); the block-per-row kernel (MIT_CE_BLOCK) leaves every column >= V
+ *     untouched.
+ * mit_cross_entropy_plan: the kernel mit_cross_entropy would launch (same host decision function; no launch,
+ * nothing dereferenced), -1 for arguments it rejects (logits NULL, ld < V): MIT_CE_ROWS (ce_rows_bf16) for bf16
+ * with row_loss != NULL, V <= 10240, ld % 8 == 0, ld >= round8(V) and logits 16-B aligned; MIT_CE_BLOCK
+ * (ce_kernel<T>) otherwise. */
+enum { MIT_CE_BLOCK = 0, MIT_CE_ROWS = 1 };
+int mit_cross_entropy_plan(int dtype, long rows, long V, const void* logits, long ld, const float* row_loss);
 int mit_count_targets(const int64_t* targets, long n, int ignore_index, float* count, void* stream);
 int mit_cross_entropy(int dtype, long rows, long V, void* logits, long ld, const int64_t* targets, int ignore_index,
                       const float* count, float* loss_sum, int want_grad, float* row_loss, void* stream);
 int mit_scalar_div(const float* a, const float* b, float* out, void* stream);
 
-/* bias gradient: out[n] (+)= sum_m dy[m*ld + n]  (f32 out; accumulate flag) */
+/* bias gradient: out[n] (+)= sum_m dy[m*ld + n]  (f32 out; accumulate flag; M == 0: out = 0, or unchanged with
+ * accumulate). ws: mit_colsum_ws_floats(M, N) floats (one partial row per 128 rows of dy). */
 int mit_colsum(int dtype, long M, long N, const void* dy, long ld, float* out, int accumulate, float* ws, void* stream);
 long mit_colsum_ws_floats(long M, long N);
 
@@ -361,7 +397,12 @@ long mit_colsum_ws_floats(long M, long N);
  * fused with torch.optim.AdamW (train.py:100,319-325; torch/optim/adam.py:419-547) over ONE flat
  * f32 parameter buffer. Sequence per step: mit_grad_norm (total norm + clip coefficient into
  * `norm_out` = {total_norm, coef}) then mit_adamw (reads coef, lr and the step count from device
- * memory, increments nothing — mit_step_inc bumps the device step counter first). */
+ * memory, increments nothing — mit_step_inc bumps the device step counter first).
+ * grad_norm: coef = min(1, max_norm / (total_norm + 1e-6)), and exactly 1 for max_norm <= 0; grads 16-B aligned.
+ * adamw (one step from the given state, t = *step >= 1, g' = coef * g; norm_out == NULL: coef = 1):
+ *   p *= 1 - lr*wd;  m += (1 - b1)(g' - m);  v = b2 v + (1 - b2) g'^2;
+ *   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps);  shadow_bf16 (may be NULL) = bf16(p).
+ *   param / grad / m / v 16-B aligned, shadow 8-B aligned; any n (the n % 4 tail is a scalar loop). */
 long mit_grad_norm_ws_floats(long n);
 int mit_grad_norm(const float* grads, long n, float max_norm, float* ws, float* norm_out, void* stream);
 int mit_step_inc(int64_t* step, void* stream);
@@ -468,7 +509,12 @@ int mit_decode_layernorm(long M, long W, const float* z, long ldz, const float* 
 /* ---------------------------------------------------------------------------------------------
  * Utilities. cast: f32 -> operand dtype copy (weights to the bf16 shadow); fill f32.
  * dropout_mask_debug: writes the keep-multiplier (0 or 1/(1-p)) the kernels use at
- * (seed, site, idx) for idx in [0, n) — tests rebuild reference masks from it. */
+ * (seed, site, idx) for idx in [0, n) — tests rebuild reference masks from it.
+ * The rule (csrc/common.h), all arithmetic modulo 2^32 unless said: key = (seed ? *seed : 0) ^
+ * (0xD6E8FEB86659FD93 * (site + 1) mod 2^64); k = lo32(key) ^ (hi32(key) * 0x9E3779B9);
+ * h = lowbias32((lo32(idx) ^ k) + rotl16(hi32(idx))), lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+ * x *= 0x846ca68b; x ^= x >> 16. Element idx is kept iff h >= (uint32)min(p * 2^32, 2^32 - 1) (p as the f32
+ * passed, the product in double), and a kept element's multiplier is the f32 quotient 1 / (1 - p). */
 int mit_cast_f32(int dtype, long n, const float* src, void* dst, void* stream);
 /* zero `bytes` bytes at p (hipMemsetAsync on the stream; graph-capturable) */
 int mit_zero(void* p, long bytes, void* stream);

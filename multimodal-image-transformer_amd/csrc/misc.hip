@@ -535,13 +535,62 @@ inline unsigned grid_for(long n, int block = 256, long cap = 8192) {
     }                                 \
   } while (0)
 
+// The host decision functions: each entry point launches what its function returns, and the mit_*_plan query of
+// include/mit_hip.h reports the same value without launching (tests/misc_contract.py).
+static int plan_im2col(int dtype, long B, long C, long H, long W, long P, const float* img, const void* out, long kpad) {
+  const long total = B * (H / P) * (W / P) * kpad;
+  return (dtype == MIT_BF16 && P % 8 == 0 && W % 4 == 0 && kpad % 8 == 0 && ((uintptr_t)img % 16) == 0 &&
+          ((uintptr_t)out % 16) == 0 && total / 8 < INT32_MAX && B * C * H * W < INT32_MAX)
+             ? MIT_ELT_VEC8
+             : MIT_ELT_SCALAR;
+}
+static int plan_assemble(int dtype, long B, long np, long E, const void* patch, const float* cls, const float* pos,
+                         const void* h) {
+  const long total = B * (np + 1) * E;
+  return (dtype == MIT_BF16 && E % 8 == 0 && ((uintptr_t)patch % 16) == 0 && ((uintptr_t)h % 16) == 0 &&
+          ((uintptr_t)cls % 16) == 0 && ((uintptr_t)pos % 16) == 0 && total / 8 < INT32_MAX)
+             ? MIT_ELT_VEC8
+             : MIT_ELT_SCALAR;
+}
+static int plan_ce(int dtype, long V, const void* logits, long ld, const float* row_loss) {
+  return (row_loss && dtype == MIT_BF16 && V <= CE_NCH * 512 && ld % 8 == 0 && (V % 8 == 0 || ld >= (V + 7) / 8 * 8) &&
+          ((uintptr_t)logits % 16) == 0)
+             ? MIT_CE_ROWS
+             : MIT_CE_BLOCK;
+}
+// keys per thread of the one-workgroup sort: n rounded up to a power of two (1024 at least) over 1024 threads
+static int plan_embed_kpt(long n) {
+  int np2 = 1024;
+  while (np2 < n) np2 <<= 1;
+  return np2 / 1024;
+}
+
+extern "C" int mit_im2col_plan(int dtype, long B, long C, long H, long W, long P, const float* img, const void* out,
+                               long kpad) {
+  if (!(img && out && P > 0 && H % P == 0 && W % P == 0 && kpad >= C * P * P)) return -1;
+  return plan_im2col(dtype, B, C, H, W, P, img, out, kpad);
+}
+extern "C" int mit_vit_assemble_plan(int dtype, long B, long np, long E, const void* patch, const float* cls,
+                                     const float* pos, const void* h) {
+  if (!(patch && cls && pos && h)) return -1;
+  return plan_assemble(dtype, B, np, E, patch, cls, pos, h);
+}
+extern "C" int mit_cross_entropy_plan(int dtype, long rows, long V, const void* logits, long ld, const float* row_loss) {
+  (void)rows;
+  if (!logits || ld < V) return -1;
+  return plan_ce(dtype, V, logits, ld, row_loss);
+}
+extern "C" int mit_embed_plan_keys_per_thread(long n) {
+  if (n < 0 || n > EMB_PLAN_MAX) return -1;
+  return n == 0 ? 0 : plan_embed_kpt(n);
+}
+
 extern "C" int mit_im2col(int dtype, long B, long C, long H, long W, long P, const float* img, void* out, long kpad,
                           void* stream) {
   MIT_RECORD([=]() { return mit_im2col(dtype, B, C, H, W, P, img, out, kpad, stream); });
   MIT_CHECK_ARG(img && out && P > 0 && H % P == 0 && W % P == 0 && kpad >= C * P * P, "mit_im2col: bad arguments");
   const long total = B * (H / P) * (W / P) * kpad;
-  if (dtype == MIT_BF16 && P % 8 == 0 && W % 4 == 0 && kpad % 8 == 0 && ((uintptr_t)img % 16) == 0 &&
-      ((uintptr_t)out % 16) == 0 && total / 8 < INT32_MAX && B * C * H * W < INT32_MAX) {
+  if (plan_im2col(dtype, B, C, H, W, P, img, out, kpad) == MIT_ELT_VEC8) {
     hipLaunchKernelGGL(im2col8_kernel, dim3(grid_for(total / 8)), dim3(256), 0, (hipStream_t)stream, (int)B, (int)C,
                        (int)H, (int)W, (int)P, img, (bf16*)out, (int)kpad);
     MIT_LAUNCH_CHECK("mit_im2col");
@@ -558,8 +607,7 @@ extern "C" int mit_vit_assemble(int dtype, long B, long np, long E, const void* 
   MIT_RECORD([=]() { return mit_vit_assemble(dtype, B, np, E, patch, cls, pos, h, stream); });
   MIT_CHECK_ARG(patch && cls && pos && h, "mit_vit_assemble: null pointer");
   const long total = B * (np + 1) * E;
-  if (dtype == MIT_BF16 && E % 8 == 0 && ((uintptr_t)patch % 16) == 0 && ((uintptr_t)h % 16) == 0 &&
-      ((uintptr_t)cls % 16) == 0 && ((uintptr_t)pos % 16) == 0 && total / 8 < INT32_MAX) {
+  if (plan_assemble(dtype, B, np, E, patch, cls, pos, h) == MIT_ELT_VEC8) {
     hipLaunchKernelGGL(assemble8_kernel, dim3(grid_for(total / 8)), dim3(256), 0, (hipStream_t)stream, (int)B, (int)np,
                        (int)E, (const bf16*)patch, cls, pos, (bf16*)h);
     MIT_LAUNCH_CHECK("mit_vit_assemble");
@@ -594,9 +642,8 @@ extern "C" int mit_embed_plan(const int64_t* tokens, long n, int* plan, void* st
   MIT_CHECK_ARG(tokens && plan && n >= 0 && n <= EMB_PLAN_MAX, "mit_embed_plan: n = %ld positions (max %d)", n,
                 EMB_PLAN_MAX);
   if (n == 0) return MIT_OK;
-  int np2 = 1;
-  while (np2 < n) np2 <<= 1;
-  if (np2 < 1024) np2 = 1024;  // one key slot per thread at least (pads sort last)
+  const int kpt = plan_embed_kpt(n);
+  const int np2 = kpt * 1024;  // one key slot per thread at least (pads sort last)
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)embed_plan_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -606,7 +653,7 @@ extern "C" int mit_embed_plan(const int64_t* tokens, long n, int* plan, void* st
     attr = true;
   }
   hipStream_t s = (hipStream_t)stream;
-  switch (np2 / 1024) {
+  switch (kpt) {
     case 1: hipLaunchKernelGGL(embed_plan_kernel<1>, dim3(1), dim3(1024), np2 * 8, s, tokens, (int)n, np2, plan); break;
     case 2: hipLaunchKernelGGL(embed_plan_kernel<2>, dim3(1), dim3(1024), np2 * 8, s, tokens, (int)n, np2, plan); break;
     case 4: hipLaunchKernelGGL(embed_plan_kernel<4>, dim3(1), dim3(1024), np2 * 8, s, tokens, (int)n, np2, plan); break;
@@ -661,8 +708,7 @@ extern "C" int mit_cross_entropy(int dtype, long rows, long V, void* logits, lon
   MIT_CHECK_ARG(logits && targets && loss_sum && (!want_grad || count), "mit_cross_entropy: null pointer");
   MIT_CHECK_ARG(ld >= V, "mit_cross_entropy: ld < V");
   if (rows <= 0) return MIT_OK;
-  if (row_loss && dtype == MIT_BF16 && V <= CE_NCH * 512 && ld % 8 == 0 && (V % 8 == 0 || ld >= (V + 7) / 8 * 8) &&
-      ((uintptr_t)logits % 16) == 0) {
+  if (plan_ce(dtype, V, logits, ld, row_loss) == MIT_CE_ROWS) {
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(ce_rows_bf16, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, rows, V, (bf16*)logits, ld,
                        targets, ignore_index, count, row_loss, want_grad);

@@ -27,7 +27,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MIT_HIP_LIB", os.path.join(_HERE, "lib", "libmit_hip.so"))
-ABI_VERSION = 7  # mit_abi_version() of the library this binding matches (include/mit_hip.h)
+ABI_VERSION = 8  # mit_abi_version() of the library this binding matches (include/mit_hip.h)
 ARGMAX_SLOTS = 16  # MIT_ARGMAX_SLOTS: slots per row of the decode head's argmax keys
 
 F32, BF16 = 0, 1
@@ -98,6 +98,8 @@ class LnPlan(ctypes.Structure):
 
 # mit_ln_plan.fwd / .bwd
 LN_SCALAR, LN_VEC4, LN_WIDE, LN_PAIR = 0, 1, 2, 3
+CE_BLOCK, CE_ROWS = 0, 1      # mit_cross_entropy_plan
+ELT_SCALAR, ELT_VEC8 = 0, 1   # mit_im2col_plan / mit_vit_assemble_plan
 
 
 # name -> (restype, argtypes); mirrors include/mit_hip.h one to one
@@ -125,6 +127,10 @@ SIGNATURES = {
                                ctypes.POINTER(AttnPlan)]),
     "mit_im2col": (I, [I, L, L, L, L, L, vp, vp, L, vp]),
     "mit_vit_assemble": (I, [I, L, L, L, vp, vp, vp, vp, vp]),
+    "mit_im2col_plan": (I, [I, L, L, L, L, L, vp, vp, L]),
+    "mit_vit_assemble_plan": (I, [I, L, L, L, vp, vp, vp, vp]),
+    "mit_cross_entropy_plan": (I, [I, L, L, vp, L, vp]),
+    "mit_embed_plan_keys_per_thread": (I, [L]),
     "mit_embed_fwd": (I, [I, L, L, L, vp, vp, Fl, vp, Fl, vp, U32, vp, vp]),
     "mit_embed_bwd": (I, [I, L, L, L, vp, vp, Fl, Fl, vp, U32, I, vp, vp, vp]),
     "mit_embed_plan_ints": (L, [L]),
@@ -669,8 +675,9 @@ def attn_grads(dout, do_row, do_batch, dq, dq_row, dq_batch, dk, dk_row, dk_batc
                      dv_row, dv_batch, ptr(delta_ws))
 
 
-def im2col(img, out, patch, kpad):
-    B, C, H, W = img.shape
+def im2col(img, out, patch, kpad, *, shape=None):
+    """shape = (B, C, H, W) when img is not a tensor of that shape (a window of a larger buffer)"""
+    B, C, H, W = shape if shape is not None else img.shape
     _check(lib().mit_im2col(dtype_code(out), B, C, H, W, patch, ptr(img), ptr(out), kpad, stream_ptr()), "mit_im2col")
 
 
@@ -679,9 +686,29 @@ def vit_assemble(patch_out, cls, pos, h, B, np_, E):
            "mit_vit_assemble")
 
 
-def embed_fwd(tokens, table, scale, pe, out, *, drop_p=0.0, seed=None, site=0):
-    B, T = tokens.shape
-    d = table.shape[1]
+def im2col_plan(dtype, shape, patch, img, out, kpad) -> int:
+    """ELT_VEC8 / ELT_SCALAR: the kernel im2col would launch (host only); -1 for rejected arguments"""
+    B, C, H, W = shape
+    return lib().mit_im2col_plan(dtype, B, C, H, W, patch, ptr(img), ptr(out), kpad)
+
+
+def vit_assemble_plan(dtype, B, np_, E, patch_out, cls, pos, h) -> int:
+    return lib().mit_vit_assemble_plan(dtype, B, np_, E, ptr(patch_out), ptr(cls), ptr(pos), ptr(h))
+
+
+def cross_entropy_plan(dtype, rows, V, logits, ld, row_loss) -> int:
+    """CE_ROWS / CE_BLOCK: the kernel cross_entropy would launch (host only); -1 for rejected arguments"""
+    return lib().mit_cross_entropy_plan(dtype, rows, V, ptr(logits), ld, ptr(row_loss))
+
+
+def embed_plan_keys_per_thread(n) -> int:
+    return lib().mit_embed_plan_keys_per_thread(n)
+
+
+def embed_fwd(tokens, table, scale, pe, out, *, drop_p=0.0, seed=None, site=0, B=None, T=None, d=None):
+    if B is None or T is None:
+        B, T = tokens.shape
+    d = d if d is not None else table.shape[1]
     _check(lib().mit_embed_fwd(dtype_code(out), B, T, d, ptr(tokens), ptr(table), scale, ptr(pe), drop_p, ptr(seed),
                                site, ptr(out), stream_ptr()), "mit_embed_fwd")
 
@@ -690,21 +717,24 @@ def embed_plan_ints(n):
     return lib().mit_embed_plan_ints(n)
 
 
-def embed_plan(tokens, plan):
+def embed_plan(tokens, plan, n=None):
     """plan (int32 [embed_plan_ints(tokens.numel())]) <- the deterministic scatter order of tokens."""
-    _check(lib().mit_embed_plan(ptr(tokens), tokens.numel(), ptr(plan), stream_ptr()), "mit_embed_plan")
+    _check(lib().mit_embed_plan(ptr(tokens), tokens.numel() if n is None else n, ptr(plan), stream_ptr()),
+           "mit_embed_plan")
 
 
-def embed_bwd(tokens, dx, scale, dtable, pad_idx, *, drop_p=0.0, seed=None, site=0, plan=None):
+def embed_bwd(tokens, dx, scale, dtable, pad_idx, *, drop_p=0.0, seed=None, site=0, plan=None, B=None, T=None,
+              d=None):
     """plan from embed_plan(tokens): deterministic; None: float atomics."""
-    B, T = tokens.shape
-    d = dtable.shape[1]
+    if B is None or T is None:
+        B, T = tokens.shape
+    d = d if d is not None else dtable.shape[1]
     _check(lib().mit_embed_bwd(dtype_code(dx), B, T, d, ptr(tokens), ptr(dx), scale, drop_p, ptr(seed), site,
                                pad_idx, ptr(plan), ptr(dtable), stream_ptr()), "mit_embed_bwd")
 
 
-def count_targets(targets, ignore_index, count):
-    _check(lib().mit_count_targets(ptr(targets), targets.numel(), ignore_index, ptr(count), stream_ptr()),
+def count_targets(targets, ignore_index, count, n=None):
+    _check(lib().mit_count_targets(ptr(targets), targets.numel() if n is None else n, ignore_index, ptr(count), stream_ptr()),
            "mit_count_targets")
 
 
@@ -741,8 +771,8 @@ def grad_norm_ws_floats(n):
     return lib().mit_grad_norm_ws_floats(n)
 
 
-def grad_norm(grads, max_norm, ws, norm_out):
-    _check(lib().mit_grad_norm(ptr(grads), grads.numel(), max_norm, ptr(ws), ptr(norm_out), stream_ptr()),
+def grad_norm(grads, max_norm, ws, norm_out, n=None):
+    _check(lib().mit_grad_norm(ptr(grads), grads.numel() if n is None else n, max_norm, ptr(ws), ptr(norm_out), stream_ptr()),
            "mit_grad_norm")
 
 
@@ -755,13 +785,13 @@ def step_inc(step):
     _check(lib().mit_step_inc(ptr(step), stream_ptr()), "mit_step_inc")
 
 
-def adamw(param, grad, m, v, shadow, norm_out, lr, step, beta1, beta2, eps, weight_decay):
-    _check(lib().mit_adamw(param.numel(), ptr(param), ptr(grad), ptr(m), ptr(v), ptr(shadow), ptr(norm_out), ptr(lr),
+def adamw(param, grad, m, v, shadow, norm_out, lr, step, beta1, beta2, eps, weight_decay, n=None):
+    _check(lib().mit_adamw(param.numel() if n is None else n, ptr(param), ptr(grad), ptr(m), ptr(v), ptr(shadow), ptr(norm_out), ptr(lr),
                            ptr(step), beta1, beta2, eps, weight_decay, stream_ptr()), "mit_adamw")
 
 
-def cast_f32(src, dst):
-    _check(lib().mit_cast_f32(dtype_code(dst), src.numel(), ptr(src), ptr(dst), stream_ptr()), "mit_cast_f32")
+def cast_f32(src, dst, n=None):
+    _check(lib().mit_cast_f32(dtype_code(dst), src.numel() if n is None else n, ptr(src), ptr(dst), stream_ptr()), "mit_cast_f32")
 
 
 def dropout_mask(n, p, seed, site, out):
