@@ -34,6 +34,9 @@ enum { MIT_K_CONTIG = 0, MIT_MN_CONTIG = 1 };
 enum { MIT_ACT_NONE = 0, MIT_ACT_RELU = 1, MIT_ACT_GELU = 2, MIT_ACT_QUICK_GELU = 3 };
 /* slots per row of the decode head's argmax keys (mit_decode_gemm_args.argmax_keys, mit_greedy_pick_keys) */
 #define MIT_ARGMAX_SLOTS 16
+/* mit_attention_decode_plan: one block per (batch, head); one block per image (bf16, H*Dh = 512) with pos;
+ * the same without pos (non-temporal K / V loads) */
+enum { MIT_DECODE_ATTN_BH = 0, MIT_DECODE_ATTN_ROWS = 1, MIT_DECODE_ATTN_ROWS_NT = 2 };
 
 const char* mit_last_error(void);
 int mit_abi_version(void);
@@ -424,11 +427,26 @@ int mit_adamw(long n, float* param, const float* grad, float* m, float* v, void*
  *   else the fixed Lk (cross-attention over the image memory). Key j is masked when
  *   key_tokens[b*tok_batch + j] == pad_idx (the reference's key-padding mask, utils.py:47-70), when
  *   key_tokens != NULL. Head dim Dh in {16, 32, 64, 128}, heads at column h*Dh. All keys masked -> NaN.
+ *   The argument Lk is ignored when pos != NULL. Tokens, K and V rows at j >= Lk are never read (they may
+ *   hold anything, NaN included), nor is anything between the batches' rows or past column H*Dh of a row;
+ *   a masked key's K / V row is read but has weight exactly 0 whatever finite values it holds. q, k, v, o
+ *   and every stride in bytes must be 16-B aligned; pos and key_tokens are not written. B = 0 launches nothing.
  * kv_store: cache[b*c_batch + (*pos)*c_row + e] = src[b*s_batch + e], e < n.
  * embed_decode: out[b, :] = table[ids[b*ld_ids + *pos]] * scale + pe[*pos]   (decoder.py:168-171)
  * greedy_pick: ids[b*ld_ids + *pos + 1] = argmax_v logits[b*ld + v] (first maximal index, like
  *   torch.argmax, model.py:236) for rows not yet finished (finished rows get pad_id); a row whose
- *   pick is end_id sets finished[b] = 1 and increments *n_finished (int32 device scalars). */
+ *   pick is end_id sets finished[b] = 1 and increments *n_finished (int32 device scalars). A finished row
+ *   is not counted again, whatever its argmax. Order of the pick: a NaN is larger than every number (the
+ *   first NaN of the row wins, as torch.argmax); -0.0 and +0.0 are equal (the first of them wins); a row of
+ *   -inf only picks column 0. Columns V .. ld-1 are never read; ids columns other than *pos + 1 are not written.
+ *   16-B loads are used when V % 4 == 0, ld % 4 == 0 and logits is 16-B aligned, 4-B loads otherwise (decided
+ *   on the device; the result is the same).
+ * mit_attention_decode_plan: the kernel family (MIT_DECODE_ATTN_*) mit_attention_decode would launch for these
+ *   arguments, from the same host decision function; -1 for arguments it rejects. No launch, no pointer is
+ *   dereferenced, no GPU needed (tests/decode_contract.py). */
+int mit_attention_decode_plan(int dtype, long B, long H, long Dh, const void* q, long q_batch, const void* k, long k_row,
+                              long k_batch, const void* v, long v_row, long v_batch, const void* o, long o_batch, long Lk,
+                              const int64_t* pos, const int64_t* key_tokens);
 int mit_attention_decode(int dtype, long B, long H, long Dh, const void* q, long q_batch, const void* k, long k_row,
                          long k_batch, const void* v, long v_row, long v_batch, void* o, long o_batch, long Lk,
                          const int64_t* pos, const int64_t* key_tokens, long tok_batch, int pad_idx, float scale,
@@ -460,7 +478,12 @@ int mit_greedy_pick_keys(long B, unsigned long long* keys, int64_t* ids, long ld
  *   NEXT LayerNorm) with stats_out [M][ceil(N/64)][2] = per 64-column tile (mean, M2) of each row,
  *   merged exactly by the consumer (Chan); cache (bf16, may be NULL): for columns n >= kv_col0,
  *   cache[m*c_batch + (*pos)*c_row + n - kv_col0] = C value (the self-attention K|V row of this token).
- * LayerNorm eps = eps for both A and the residual. ReLU only without a residual. */
+ * LayerNorm eps = eps for both A and the residual. ReLU only without a residual.
+ * May be NULL: bias, C (with z_out or argmax_keys given), z_out, stats_out (needs z_out), cache, r (r_mode 0).
+ * A, B, C, z_out, r, cache, gamma and beta pointers 16-B aligned; a_stats, r_stats and stats_out 8-B aligned
+ * ((mean, M2) pairs, [row][ceil(width / 64)][2] dense); bias 4-B. Pad columns (>= K of A and B, >= N of r), rows
+ * >= M of A / r / the statistics, rows >= N of B and bias past N are never read; of the cache only row *pos is
+ * written. */
 typedef struct {
   long M, N, K;
   const void* A;
@@ -491,7 +514,8 @@ typedef struct {
   /* argmax_keys (u64 [MIT_ARGMAX_SLOTS][M], NULL: off): the greedy pick folded into the vocabulary head.
    * Each 64-column block's maximum of row m over act(A . B^T + bias) leaves as one atomic max of
    * ord(value) << 32 | (0xFFFFFFFF - column) (ord: the order-preserving u32 image of an f32, NaN
-   * largest) into slot (column block % MIT_ARGMAX_SLOTS) of the row, so the largest key over the row's
+   * largest; -0.0 orders just below +0.0 here, where mit_greedy_pick takes them as equal) into slot (column
+   * block % MIT_ARGMAX_SLOTS) of the row, so the largest key over the row's
    * slots is its first maximal column (torch.argmax). The slots spread the atomics: with one key per
    * row all 157 column blocks of a 10000-word head hit the same 32 cache lines of 256 rows' keys, and the
    * memory-side atomics on them serialised the launch (~29 us per token step). bf16 A rows, no residual
@@ -501,6 +525,16 @@ typedef struct {
   unsigned long long* argmax_keys;
 } mit_decode_gemm_args;
 int mit_decode_gemm(const mit_decode_gemm_args* args, void* stream);
+/* What mit_decode_gemm would launch for these arguments, from the same host decision function: the kernel
+ * instantiation (a_mode: 0 bf16 A, 1 LN(A); act; r_mode: 0 / 1 / 2, 3 = the argmax epilogue; c_f32), the launch
+ * shape (waves x block_rows: 4 x 64 or 8 x 32 rows of a 64-column tile), the grid (0 when M == 0: nothing is
+ * launched) and the dynamic LDS bytes. Returns 0, or -1 for arguments mit_decode_gemm rejects. No launch, no
+ * pointer is dereferenced, no GPU needed. */
+typedef struct {
+  int a_mode, act, r_mode, c_f32, waves, block_rows;
+  long grid, lds_bytes;
+} mit_decode_gemm_plan_t;
+int mit_decode_gemm_plan(const mit_decode_gemm_args* args, mit_decode_gemm_plan_t* out);
 /* out[m, :] = LN(z[m, :]) (bf16) from the statistics a mit_decode_gemm stats_out wrote (W <= 1024):
  * the vocabulary head's operand, which then runs on mit_gemm. */
 int mit_decode_layernorm(long M, long W, const float* z, long ldz, const float* stats, const float* gamma,

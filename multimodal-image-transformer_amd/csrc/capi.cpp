@@ -24,7 +24,7 @@ int mit_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* mit_last_error(void) { return g_err; }
-extern "C" int mit_abi_version(void) { return 8; }
+extern "C" int mit_abi_version(void) { return 9; }
 
 // ---------------------------------------------------------------------------------------------
 // launch plans

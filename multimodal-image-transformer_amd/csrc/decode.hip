@@ -754,11 +754,11 @@ inline unsigned grid_for(long n, int block = 256, long cap = 8192) {
     }                                 \
   } while (0)
 
-extern "C" int mit_attention_decode(int dtype, long B, long H, long Dh, const void* q, long q_batch, const void* k,
-                                    long k_row, long k_batch, const void* v, long v_row, long v_batch, void* o,
-                                    long o_batch, long Lk, const int64_t* pos, const int64_t* key_tokens,
-                                    long tok_batch, int pad_idx, float scale, void* stream) {
-  MIT_RECORD([=]() { return mit_attention_decode(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, Lk, pos, key_tokens, tok_batch, pad_idx, scale, stream); });
+// which kernel a mit_attention_decode call launches (MIT_DECODE_ATTN_*), shared by the entry point and
+// mit_attention_decode_plan; host arithmetic only, no pointer is dereferenced
+static int plan_attn_decode(int dtype, long B, long H, long Dh, const void* q, long q_batch, const void* k, long k_row,
+                            long k_batch, const void* v, long v_row, long v_batch, const void* o, long o_batch, long Lk,
+                            const int64_t* pos, int* family) {
   MIT_CHECK_ARG(q && k && v && o, "mit_attention_decode: null pointer");
   MIT_CHECK_ARG(Dh == 16 || Dh == 32 || Dh == 64 || Dh == 128, "mit_attention_decode: head_dim %ld unsupported", Dh);
   MIT_CHECK_ARG(dtype == MIT_BF16 || dtype == MIT_F32, "mit_attention_decode: bad dtype");
@@ -768,12 +768,39 @@ extern "C" int mit_attention_decode(int dtype, long B, long H, long Dh, const vo
                     (q_batch * esz) % 16 == 0 && (k_row * esz) % 16 == 0 && (k_batch * esz) % 16 == 0 &&
                     (v_row * esz) % 16 == 0 && (v_batch * esz) % 16 == 0 && (o_batch * esz) % 16 == 0,
                 "mit_attention_decode: rows must be 16-B aligned");
+  // d_model = 512 in bf16: one block per image reads whole 1-KiB rows; without a position (the cross-attention's
+  // fixed memory) the once-read K / V stream non-temporally
+  if (dtype == MIT_BF16 && H * Dh == 512 && B < (1L << 31))
+    *family = pos == nullptr ? MIT_DECODE_ATTN_ROWS_NT : MIT_DECODE_ATTN_ROWS;
+  else
+    *family = MIT_DECODE_ATTN_BH;
+  return MIT_OK;
+}
+
+extern "C" int mit_attention_decode_plan(int dtype, long B, long H, long Dh, const void* q, long q_batch, const void* k,
+                                         long k_row, long k_batch, const void* v, long v_row, long v_batch, const void* o,
+                                         long o_batch, long Lk, const int64_t* pos, const int64_t* key_tokens) {
+  (void)key_tokens;  // the mask is a kernel argument of every family, never a dispatch predicate
+  int family = -1;
+  if (plan_attn_decode(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, Lk, pos, &family) != MIT_OK)
+    return -1;
+  return family;
+}
+
+extern "C" int mit_attention_decode(int dtype, long B, long H, long Dh, const void* q, long q_batch, const void* k,
+                                    long k_row, long k_batch, const void* v, long v_row, long v_batch, void* o,
+                                    long o_batch, long Lk, const int64_t* pos, const int64_t* key_tokens,
+                                    long tok_batch, int pad_idx, float scale, void* stream) {
+  MIT_RECORD([=]() { return mit_attention_decode(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, Lk, pos, key_tokens, tok_batch, pad_idx, scale, stream); });
+  int family = -1;
+  const int rc = plan_attn_decode(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, Lk, pos, &family);
+  if (rc != MIT_OK) return rc;
   if (B <= 0 || H <= 0) return MIT_OK;
-  if (dtype == MIT_BF16 && H * Dh == 512 && B < (1L << 31)) {
+  if (family != MIT_DECODE_ATTN_BH) {
     // the cross-attention's fixed memory K/V (no position: 620 MB per cfg1 token step, far past the 256 MB
     // Infinity Cache) streams non-temporally, so the layers' weights and self-attention caches stay
     // cached between token steps: 371.8-372.6 k -> 383.3-383.8 k tokens/s (configs[4], one box)
-    const bool nt = pos == nullptr;
+    const bool nt = family == MIT_DECODE_ATTN_ROWS_NT;
 #define MIT_ROWS_LAUNCH(DH_)                                                                                          \
   if (nt)                                                                                                             \
     hipLaunchKernelGGL((attn_decode_rows_kernel<DH_, 8, true>), dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream, \
@@ -901,39 +928,27 @@ extern "C" int mit_greedy_pick_advance(long B, long V, const float* logits, long
 
 namespace {
 template <int AMODE, int ACT, int RMODE, bool CF32, int NW, int BMR>
-int launch_decode_gemm_nw(const mit_decode_gemm_args* g, hipStream_t s) {
-  const long nblk = ((g->M + BMR - 1) / BMR) * ((g->N + 63) / 64);
-  const int red = NW * BMR * DG_RLD * 4;
-  const int lds = AMODE ? (int)max((long)BMR * (g->K * 2 + 16), (long)red) : red;
+int launch_decode_gemm_nw(const mit_decode_gemm_args* g, hipStream_t s, const mit_decode_gemm_plan_t& p) {
+  const int lds = (int)p.lds_bytes;
   static int attr = 0;
   if (attr < lds) {
     (void)hipFuncSetAttribute((const void*)decode_gemm_kernel<AMODE, ACT, RMODE, CF32, NW, BMR>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr = lds;
   }
-  hipLaunchKernelGGL((decode_gemm_kernel<AMODE, ACT, RMODE, CF32, NW, BMR>), dim3((unsigned)nblk), dim3(NW * 64), lds, s, *g);
+  hipLaunchKernelGGL((decode_gemm_kernel<AMODE, ACT, RMODE, CF32, NW, BMR>), dim3((unsigned)p.grid), dim3(NW * 64), lds, s, *g);
   MIT_LAUNCH_CHECK("mit_decode_gemm");
   return MIT_OK;
 }
-// bf16 operand with K >= 512 (linear2 at K = d_ff, and since round 3 the K = 512 residual-LN GEMMs
-// self-out / cross-out): 8 waves split K over 32 x 64 tiles (twice the blocks, a quarter of the K
-// steps per wave: the K loop is one L2 round trip per step). Threshold K >= 512 vs 1024: 782 vs 824 us
-// per token step at B = 256, interleaved on one box. The LN-operand GEMMs (in_proj, cross-q, linear1,
-// head) on 8 waves x 32 rows as well (4 rows staged per wave): 782 -> 730 us per token step.
 template <int AMODE, int ACT, int RMODE, bool CF32>
-int launch_decode_gemm(const mit_decode_gemm_args* g, hipStream_t s) {
-  // the vocabulary head (argmax epilogue, N = 10000): 4 waves x 64 rows, half the blocks of the 8-wave
-  // form and each weight block read by 4 instead of 8 row blocks (with the column-major block order:
-  // 700 -> 690 us per token step at B = 256)
-  if (RMODE == 3) return launch_decode_gemm_nw<AMODE, ACT, RMODE, CF32, 4, 64>(g, s);
-  if (AMODE != 0 || g->K >= 512) return launch_decode_gemm_nw<AMODE, ACT, RMODE, CF32, 8, 32>(g, s);
-  return launch_decode_gemm_nw<AMODE, ACT, RMODE, CF32, 4, 64>(g, s);
+int launch_decode_gemm(const mit_decode_gemm_args* g, hipStream_t s, const mit_decode_gemm_plan_t& p) {
+  if (p.waves == 8) return launch_decode_gemm_nw<AMODE, ACT, RMODE, CF32, 8, 32>(g, s, p);
+  return launch_decode_gemm_nw<AMODE, ACT, RMODE, CF32, 4, 64>(g, s, p);
 }
-}  // namespace
 
-extern "C" int mit_decode_gemm(const mit_decode_gemm_args* g, void* stream) {
-  MIT_CHECK_ARG(g != nullptr, "mit_decode_gemm: null args");
-  MIT_RECORD([c = *g, stream]() { return mit_decode_gemm(&c, stream); });
+// the instantiation and launch shape of a mit_decode_gemm call, shared by the entry point and
+// mit_decode_gemm_plan; host arithmetic only, no pointer is dereferenced
+int plan_decode_gemm(const mit_decode_gemm_args* g, mit_decode_gemm_plan_t* p) {
   MIT_CHECK_ARG(g->M >= 0 && g->N > 0 && g->K > 0, "mit_decode_gemm: bad extents M=%ld N=%ld K=%ld", g->M, g->N, g->K);
   MIT_CHECK_ARG(g->A && g->B, "mit_decode_gemm: null operand");
   MIT_CHECK_ARG(g->C || g->z_out || g->argmax_keys, "mit_decode_gemm: no output");
@@ -964,24 +979,62 @@ extern "C" int mit_decode_gemm(const mit_decode_gemm_args* g, void* stream) {
   MIT_CHECK_ARG(!g->argmax_keys || (!lna && g->act == MIT_ACT_NONE && g->r_mode == 0 && !g->C && !g->z_out &&
                                      !g->cache && ((uintptr_t)g->argmax_keys % 8) == 0 && g->N < (1L << 32)),
                 "mit_decode_gemm: argmax_keys needs bf16 A rows, no activation / residual / other output");
+  const bool relu = g->act == MIT_ACT_RELU;
+  p->a_mode = lna ? 1 : 0;
+  p->act = g->act;
+  p->r_mode = g->argmax_keys ? 3 : g->r_mode;
+  p->c_f32 = g->c_f32 && !g->argmax_keys ? 1 : 0;  // the argmax head writes no C: the flag is not looked at
+  if (!g->argmax_keys) {
+    if (g->c_f32) {
+      MIT_CHECK_ARG(lna && !relu && g->r_mode == 0, "mit_decode_gemm: f32 C only for the LN-operand head GEMM");
+    } else if (lna) {
+      MIT_CHECK_ARG(g->r_mode == 0, "mit_decode_gemm: LN operand with a residual unsupported");
+    } else {
+      MIT_CHECK_ARG(!relu || g->r_mode == 0, "mit_decode_gemm: ReLU with a residual unsupported");
+    }
+  }
+  // bf16 operand with K >= 512 (linear2 at K = d_ff, and since round 3 the K = 512 residual-LN GEMMs
+  // self-out / cross-out): 8 waves split K over 32 x 64 tiles (twice the blocks, a quarter of the K
+  // steps per wave: the K loop is one L2 round trip per step). Threshold K >= 512 vs 1024: 782 vs 824 us
+  // per token step at B = 256, interleaved on one box. The LN-operand GEMMs (in_proj, cross-q, linear1,
+  // head) on 8 waves x 32 rows as well (4 rows staged per wave): 782 -> 730 us per token step.
+  // The vocabulary head (argmax epilogue, N = 10000): 4 waves x 64 rows, half the blocks of the 8-wave
+  // form and each weight block read by 4 instead of 8 row blocks (with the column-major block order:
+  // 700 -> 690 us per token step at B = 256)
+  const bool wide = !g->argmax_keys && (lna || g->K >= 512);
+  p->waves = wide ? 8 : 4;
+  p->block_rows = wide ? 32 : 64;
+  p->grid = ((g->M + p->block_rows - 1) / p->block_rows) * ((g->N + 63) / 64);  // 0 when M == 0: nothing is launched
+  const long red = (long)p->waves * p->block_rows * DG_RLD * 4;
+  p->lds_bytes = lna ? max((long)p->block_rows * (g->K * 2 + 16), red) : red;
+  return MIT_OK;
+}
+}  // namespace
+
+extern "C" int mit_decode_gemm_plan(const mit_decode_gemm_args* g, mit_decode_gemm_plan_t* out) {
+  mit_decode_gemm_plan_t p;
+  if (!g || !out || plan_decode_gemm(g, &p) != MIT_OK) return -1;
+  *out = p;
+  return 0;
+}
+
+extern "C" int mit_decode_gemm(const mit_decode_gemm_args* g, void* stream) {
+  MIT_CHECK_ARG(g != nullptr, "mit_decode_gemm: null args");
+  MIT_RECORD([c = *g, stream]() { return mit_decode_gemm(&c, stream); });
+  mit_decode_gemm_plan_t p;
+  const int rc = plan_decode_gemm(g, &p);
+  if (rc != MIT_OK) return rc;
   if (g->M == 0) return MIT_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (g->argmax_keys) return launch_decode_gemm<0, MIT_ACT_NONE, 3, false>(g, s);
-  const bool relu = g->act == MIT_ACT_RELU;
-  if (g->c_f32) {
-    MIT_CHECK_ARG(lna && !relu && g->r_mode == 0, "mit_decode_gemm: f32 C only for the LN-operand head GEMM");
-    return launch_decode_gemm<1, MIT_ACT_NONE, 0, true>(g, s);
-  }
-  if (lna) {
-    MIT_CHECK_ARG(g->r_mode == 0, "mit_decode_gemm: LN operand with a residual unsupported");
-    return relu ? launch_decode_gemm<1, MIT_ACT_RELU, 0, false>(g, s) : launch_decode_gemm<1, MIT_ACT_NONE, 0, false>(g, s);
-  }
-  MIT_CHECK_ARG(!relu || g->r_mode == 0, "mit_decode_gemm: ReLU with a residual unsupported");
-  if (relu) return launch_decode_gemm<0, MIT_ACT_RELU, 0, false>(g, s);
-  switch (g->r_mode) {
-    case 1: return launch_decode_gemm<0, MIT_ACT_NONE, 1, false>(g, s);
-    case 2: return launch_decode_gemm<0, MIT_ACT_NONE, 2, false>(g, s);
-    default: return launch_decode_gemm<0, MIT_ACT_NONE, 0, false>(g, s);
+  if (p.r_mode == 3) return launch_decode_gemm<0, MIT_ACT_NONE, 3, false>(g, s, p);
+  const bool relu = p.act == MIT_ACT_RELU;
+  if (p.c_f32) return launch_decode_gemm<1, MIT_ACT_NONE, 0, true>(g, s, p);
+  if (p.a_mode) return relu ? launch_decode_gemm<1, MIT_ACT_RELU, 0, false>(g, s, p) : launch_decode_gemm<1, MIT_ACT_NONE, 0, false>(g, s, p);
+  if (relu) return launch_decode_gemm<0, MIT_ACT_RELU, 0, false>(g, s, p);
+  switch (p.r_mode) {
+    case 1: return launch_decode_gemm<0, MIT_ACT_NONE, 1, false>(g, s, p);
+    case 2: return launch_decode_gemm<0, MIT_ACT_NONE, 2, false>(g, s, p);
+    default: return launch_decode_gemm<0, MIT_ACT_NONE, 0, false>(g, s, p);
   }
 }
 

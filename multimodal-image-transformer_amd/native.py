@@ -27,7 +27,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MIT_HIP_LIB", os.path.join(_HERE, "lib", "libmit_hip.so"))
-ABI_VERSION = 8  # mit_abi_version() of the library this binding matches (include/mit_hip.h)
+ABI_VERSION = 9  # mit_abi_version() of the library this binding matches (include/mit_hip.h)
 ARGMAX_SLOTS = 16  # MIT_ARGMAX_SLOTS: slots per row of the decode head's argmax keys
 
 F32, BF16 = 0, 1
@@ -64,6 +64,15 @@ class DecodeGemmArgs(ctypes.Structure):
                 ("ldc", L), ("r_mode", I), ("r", vp), ("ldr", L), ("r_stats", vp), ("r_gamma", vp),
                 ("r_beta", vp), ("eps", Fl), ("z_out", vp), ("ldz", L), ("stats_out", vp), ("cache", vp),
                 ("c_row", L), ("c_batch", L), ("kv_col0", L), ("pos", vp), ("argmax_keys", vp)]
+
+
+class DecodeGemmPlan(ctypes.Structure):
+    _fields_ = [("a_mode", I), ("act", I), ("r_mode", I), ("c_f32", I), ("waves", I), ("block_rows", I),
+                ("grid", L), ("lds_bytes", L)]
+
+
+# mit_attention_decode_plan
+DECODE_ATTN_BH, DECODE_ATTN_ROWS, DECODE_ATTN_ROWS_NT = 0, 1, 2
 
 
 class LnGradsJob(ctypes.Structure):
@@ -149,6 +158,8 @@ SIGNATURES = {
     "mit_scalar_div": (I, [vp, vp, vp, vp]),
     "mit_dropout_mask": (I, [L, Fl, vp, U32, vp, vp]),
     "mit_attention_decode": (I, [I, L, L, L, vp, L, vp, L, L, vp, L, L, vp, L, L, vp, vp, L, I, Fl, vp]),
+    "mit_attention_decode_plan": (I, [I, L, L, L, vp, L, vp, L, L, vp, L, L, vp, L, L, vp, vp]),
+    "mit_decode_gemm_plan": (I, [ctypes.POINTER(DecodeGemmArgs), ctypes.POINTER(DecodeGemmPlan)]),
     "mit_kv_store": (I, [I, L, L, vp, L, vp, L, L, vp, vp]),
     "mit_embed_decode": (I, [I, L, L, vp, L, vp, vp, Fl, vp, vp, vp]),
     "mit_image_normalize": (I, [L, L, L, vp, vp, ctypes.POINTER(Fl), ctypes.POINTER(Fl), vp]),
@@ -805,6 +816,21 @@ def attention_decode(q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batc
     _check(lib().mit_attention_decode(dtype_code(q), B, H, Dh, ptr(q), q_batch, ptr(k), k_row, k_batch, ptr(v), v_row,
                                       v_batch, ptr(o), o_batch, Lk, ptr(pos), ptr(key_tokens), tok_batch, pad_idx,
                                       scale, stream_ptr()), "mit_attention_decode")
+
+
+def attention_decode_plan(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, *, Lk=0,
+                          pos=None, key_tokens=None) -> int:
+    """DECODE_ATTN_BH / _ROWS / _ROWS_NT: the kernel family attention_decode would launch (mit_attention_decode_plan:
+    host only, no GPU needed); -1 for rejected arguments. Pointers are integers (addresses) or None."""
+    return lib().mit_attention_decode_plan(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o,
+                                           o_batch, Lk, pos, key_tokens)
+
+
+def decode_gemm_plan(g: DecodeGemmArgs):
+    """The DecodeGemmPlan mit_decode_gemm would launch for g (host only, no GPU needed); None for rejected
+    arguments."""
+    out = DecodeGemmPlan()
+    return out if lib().mit_decode_gemm_plan(ctypes.byref(g), ctypes.byref(out)) == 0 else None
 
 
 def kv_store(src, s_batch, cache, c_row, c_batch, B, n, pos):
