@@ -541,6 +541,58 @@ int mit_decode_layernorm(long M, long W, const float* z, long ldz, const float* 
                          const float* beta, float eps, void* out, long ldo, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Beam-search decoding on the same KV-cache step (csrc/beam.hip). K = beam_size slots per image, row
+ * r = b*K + k; per slot a cumulative log-probability `score` (f32), a `finished` flag and `length`, the number
+ * of generated tokens, END included (int32). Start state: score 0 in slot 0 and -inf in the others, every slot
+ * holding START at position 0, anc[r, 0] = k.
+ * Storage is SLOT-ORDERED: row r, position j of the self-attention caches and of `tok` (int64 [R, ld_tok]) holds
+ * what slot r wrote or consumed at step j, which is what mit_decode_gemm's cache epilogue, mit_kv_store and
+ * mit_embed_decode do unchanged. `anc` (int32 [R, ld_anc]) is the ancestor table: anc[r, j] is the slot of the
+ * same image whose row holds position j of the beam now in slot r; a beam's ids are tok[b*K + anc[r, j], j].
+ *
+ * attention_decode_beam: mit_attention_decode (same contract: alignment, Lk = *pos + 1 when pos != NULL, masks,
+ *   nothing read at j >= Lk) over R rows, except for the K / V / key_tokens batch that key j of row r is read from:
+ *     anc != NULL: (r / group) * group + anc[r*ld_anc + j]   (self-attention over the slot-ordered cache; key_tokens
+ *                  = tok goes through the same index; R % group == 0; anc 4-B aligned, entries in [0, group))
+ *     anc == NULL: r / group   (the `group` beams of an image read ONE copy of the cross-attention K / V)
+ *   anc[r, j] for j >= Lk is never read, nor are cache rows only unreferenced slots hold. group = 1 with anc == NULL
+ *   IS mit_attention_decode (forwarded: bitwise the same). Every other call launches the block-per-(row, head)
+ *   family, whose arithmetic is that of mit_attention_decode's MIT_DECODE_ATTN_BH kernel: on physically gathered
+ *   K / V / tokens that kernel gives bitwise the same output.
+ * mit_attention_decode_beam_plan: the family (MIT_DECODE_ATTN_*) the call would launch, from the same host decision
+ *   function; -1 for arguments it rejects. No launch, no pointer is dereferenced, no GPU needed.
+ * beam_select: one selection step at position p = *pos for B images (R = B*K rows):
+ *   - a live slot k offers V candidates (score_k + (logits[r, v] - lse_k), parent k, token v), lse_k = m + log(sum
+ *     exp(logit - m)) in f32 with m the row maximum; a finished slot offers exactly (score_k, k, pad_id) and its
+ *     logits row is never read; columns >= V (ld padding) are never read;
+ *   - the K best by (score descending, parent ascending, token ascending) become the new slots 0 .. K-1 in that
+ *     order: score = the candidate's; finished = parent finished or token == end_id; length = the parent's, + 1
+ *     if the parent was live. (Within one parent the candidates are ranked by logit, of which the score is a
+ *     monotone function.) -0.0 and +0.0 scores are equal. Rows with NaN logits: undefined picks, but tokens stay
+ *     in [0, V) and parents in [0, K);
+ *   - tok[r, p+1] = the token; anc_new[k, 0..p] = anc_old[parent_k, 0..p] (in place, safe for any parent map),
+ *     anc_new[k, p+1] = k; *n_finished is SET to the number of finished beams; *pos = p + 1, written once after
+ *     every row has read p. Nothing else is written (tok / anc columns past p+1, other tok columns). A step at
+ *     p + 1 >= ld_tok (or ld_anc) skips the column it has no room for.
+ *   Deterministic: the lse sums run in a fixed order and every comparison is an integer one on order-preserving
+ *   keys, so a second launch on the same inputs is bitwise equal. 1 <= K <= 8, K <= V < 2^31, ld >= V; logits 4-B
+ *   aligned (16-B loads when ld % 4 == 0 and logits is 16-B aligned: the same result), ws 8-B aligned with
+ *   ws_bytes >= mit_beam_select_ws_bytes(B, K, V) (-1 for K outside 1..8): the rows' K best (score, token) pairs
+ *   between the two launches (one block per row, then one wave per image). Asynchronous, recordable. */
+int mit_attention_decode_beam_plan(int dtype, long R, long H, long Dh, const void* q, long q_batch, const void* k,
+                                   long k_row, long k_batch, const void* v, long v_row, long v_batch, const void* o,
+                                   long o_batch, long Lk, const int64_t* pos, long group, const int* anc, long ld_anc,
+                                   const int64_t* key_tokens);
+int mit_attention_decode_beam(int dtype, long R, long H, long Dh, const void* q, long q_batch, const void* k, long k_row,
+                              long k_batch, const void* v, long v_row, long v_batch, void* o, long o_batch, long Lk,
+                              const int64_t* pos, long group, const int* anc, long ld_anc, const int64_t* key_tokens,
+                              long tok_batch, int pad_idx, float scale, void* stream);
+long mit_beam_select_ws_bytes(long B, long K, long V);
+int mit_beam_select(long B, long K, long V, const float* logits, long ld, float* score, int64_t* tok, long ld_tok,
+                    int* anc, long ld_anc, int64_t* pos, int64_t end_id, int64_t pad_id, int* finished, int* length,
+                    int* n_finished, void* ws, long ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Utilities. cast: f32 -> operand dtype copy (weights to the bf16 shadow); fill f32.
  * dropout_mask_debug: writes the keep-multiplier (0 or 1/(1-p)) the kernels use at
  * (seed, site, idx) for idx in [0, n) — tests rebuild reference masks from it.

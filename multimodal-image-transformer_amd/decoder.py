@@ -259,7 +259,11 @@ class DecodeState:
     and their count, the cross-attention K/V of all layers [B*S, L*2d], per-layer self-attention
     caches [B, max_len, 2d] (K | V), and the B-row activations of one token step."""
 
-    def __init__(self, dec: "TransformerDecoder", B: int, S: int, max_len: int, start_id: int, end_id: int):
+    K = 0  # beam slots per image (BeamState); 0: greedy rows
+
+    def __init__(self, dec: "TransformerDecoder", B: int, S: int, max_len: int, start_id: int, end_id: int,
+                 images: Optional[int] = None):
+        """B rows; images: how many memories the cross-attention K/V holds (default: one per row)."""
         dev, dt = dec.device, dec.dtype
         d, F, L, V = dec.d, dec.F, dec.L, dec.V
         self.B, self.S, self.max_len, self.end_id = B, S, max_len, int(end_id)
@@ -271,7 +275,7 @@ class DecodeState:
         # per layer contiguous [L][B*S][2d] (K | V): a decode attention block (b, h) then reads its S keys
         # at a 2 KiB stride instead of the training layout's L * 2d row (12 KiB at cfg1), which left the
         # S = 197 cross attention at ~2.6 TB/s on DRAM page misses
-        self.kv = torch.empty(L, B * S, 2 * d, dtype=dt, device=dev)
+        self.kv = torch.empty(L, (B if images is None else images) * S, 2 * d, dtype=dt, device=dev)
         self.cache = [torch.empty(B, max_len, 2 * d, dtype=dt, device=dev) for _ in range(L)]
         e = lambda n: torch.empty(B, n, dtype=dt, device=dev)  # noqa: E731
         self.x, self.x1, self.x2, self.y, self.o, self.q = e(d), e(d), e(d), e(d), e(d), e(d)
@@ -292,6 +296,41 @@ class DecodeState:
         """Per row: START .. up to and including the first END (model.py:236-242), else max_len ids."""
         out = []
         for row in self.ids.cpu().tolist():
+            if self.end_id in row[1:]:
+                row = row[: row.index(self.end_id, 1) + 1]
+            out.append(row)
+        return out
+
+
+class BeamState(DecodeState):
+    """Device state of a beam search (TransformerDecoder.beam_begin / beam_step): a DecodeState of R = images * K
+    rows (row b*K + k is slot k of image b) whose caches and ids are SLOT-ORDERED -- row r, position j holds what
+    slot r wrote at step j -- plus per slot the cumulative log-probability `score`, `length` (generated tokens,
+    END included) and the ancestor table `anc` (int32 [R, max_len]): anc[r, j] is the slot of the same image whose
+    row holds position j of the beam now in slot r. The cross-attention K/V holds one memory per image."""
+
+    def __init__(self, dec: "TransformerDecoder", images: int, K: int, S: int, max_len: int, start_id: int,
+                 end_id: int):
+        super().__init__(dec, images * K, S, max_len, start_id, end_id, images=images)
+        dev = dec.device
+        self.images, self.K = images, K
+        self.score = torch.full((images, K), float("-inf"), dtype=torch.float32, device=dev)
+        self.score[:, 0] = 0.0
+        self.score = self.score.view(-1)
+        self.length = torch.zeros(images * K, dtype=torch.int32, device=dev)
+        self.anc = torch.zeros(images * K, max_len, dtype=torch.int32, device=dev)
+        self.anc[:, 0] = torch.arange(K, dtype=torch.int32, device=dev).repeat(images)
+        self.ws = torch.empty((native.beam_select_ws_bytes(images, K, dec.V) + 7) // 8, dtype=torch.int64, device=dev)
+
+    def beam_ids(self) -> torch.Tensor:
+        """int64 [images, K, max_len]: each slot's own ids, gathered through the ancestor table (one gather)."""
+        B, K, T = self.images, self.K, self.max_len
+        return self.ids.view(B, K, T).gather(1, self.anc.view(B, K, T).long())
+
+    def token_lists(self) -> List[List[int]]:
+        """Per row (image-major, slot-minor) as DecodeState.token_lists: START .. first END inclusive, else max_len."""
+        out = []
+        for row in self.beam_ids().view(self.B, self.max_len).cpu().tolist():
             if self.end_id in row[1:]:
                 row = row[: row.index(self.end_id, 1) + 1]
             out.append(row)
@@ -727,9 +766,43 @@ class TransformerDecoder:
         No host synchronisation: capturable into a hipGraph."""
         if stt.fused:
             return self._decode_step_fused(stt)
-        d, H, L, V = self.d, self.H, self.L, self.V
+        x = self._step_body(stt)
         st, w = self.store, self.store.w
-        B, S, Tm = stt.B, stt.S, stt.max_len
+        native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
+        native.greedy_pick(stt.logits, stt.ids, stt.pos, stt.end_id, self.pad_idx, stt.finished, stt.n_finished,
+                           V=self.V)
+        native.step_inc(stt.pos)
+
+    def _attn_self(self, stt: "DecodeState", cache: torch.Tensor, scale: float):
+        """The step's causal self-attention over the cache (query: stt.qkv's first d columns) -> stt.o; a beam
+        state reads each key from its ancestor's row."""
+        d, Tm = self.d, stt.max_len
+        if stt.K:
+            native.attention_decode_beam(stt.qkv, 3 * d, cache, 2 * d, Tm * 2 * d, cache[:, :, d:], 2 * d, Tm * 2 * d,
+                                         stt.o, d, stt.B, self.H, pos=stt.pos, group=stt.K, anc=stt.anc,
+                                         key_tokens=stt.ids, tok_batch=Tm, pad_idx=self.pad_idx, scale=scale,
+                                         Dh=self.hd)
+        else:
+            native.attention_decode(stt.qkv, 3 * d, cache, 2 * d, Tm * 2 * d, cache[:, :, d:], 2 * d, Tm * 2 * d, stt.o,
+                                    d, stt.B, self.H, pos=stt.pos, key_tokens=stt.ids, tok_batch=Tm,
+                                    pad_idx=self.pad_idx, scale=scale, Dh=self.hd)
+
+    def _attn_cross(self, stt: "DecodeState", kvl: torch.Tensor, scale: float):
+        """The step's cross-attention of stt.q over the image memory's K | V rows kvl -> stt.o; the K beams of an
+        image share its one K/V."""
+        d, S = self.d, stt.S
+        if stt.K:
+            native.attention_decode_beam(stt.q, d, kvl, 2 * d, S * 2 * d, kvl[:, d:], 2 * d, S * 2 * d, stt.o, d, stt.B,
+                                         self.H, Lk=S, group=stt.K, scale=scale, Dh=self.hd)
+        else:
+            native.attention_decode(stt.q, d, kvl, 2 * d, S * 2 * d, kvl[:, d:], 2 * d, S * 2 * d,
+                                    stt.o, d, stt.B, self.H, Lk=S, scale=scale, Dh=self.hd)
+
+    def _step_body(self, stt: "DecodeState") -> torch.Tensor:
+        """One token step up to the vocabulary head's operand [B, d] (unfused: any dtype)."""
+        d, L = self.d, self.L
+        st, w = self.store, self.store.w
+        B, Tm = stt.B, stt.max_len
         native.embed_decode(stt.ids, stt.pos, w("token_embedding.weight"), math.sqrt(d), self.pe, stt.x)
         x = stt.x
         for l in range(L):
@@ -737,24 +810,18 @@ class TransformerDecoder:
             cache = stt.cache[l]
             native.linear(x, w(pre + "self_in.weight"), stt.qkv, bias=st.p(pre + "self_in.bias"))
             native.kv_store(stt.qkv[:, d:], 3 * d, cache, 2 * d, Tm * 2 * d, B, 2 * d, stt.pos)
-            native.attention_decode(stt.qkv, 3 * d, cache, 2 * d, Tm * 2 * d, cache[:, :, d:], 2 * d, Tm * 2 * d, stt.o,
-                                    d, B, H, pos=stt.pos, key_tokens=stt.ids, tok_batch=Tm, pad_idx=self.pad_idx,
-                                    scale=1.0 / math.sqrt(self.hd), Dh=self.hd)
+            self._attn_self(stt, cache, 1.0 / math.sqrt(self.hd))
             native.linear(stt.o, w(pre + "self_out.weight"), stt.y, bias=st.p(pre + "self_out.bias"))
             native.layernorm_fwd(x, st.p(pre + "norm1.weight"), st.p(pre + "norm1.bias"), 1e-5, stt.x1, r=stt.y)
             native.linear(stt.x1, w(pre + "cross_q.weight"), stt.q, bias=st.p(pre + "cross_q.bias"))
-            kvl = stt.kv[l]
-            native.attention_decode(stt.q, d, kvl, 2 * d, S * 2 * d, kvl[:, d:], 2 * d, S * 2 * d,
-                                    stt.o, d, B, H, Lk=S, scale=1.0 / math.sqrt(self.hd), Dh=self.hd)
+            self._attn_cross(stt, stt.kv[l], 1.0 / math.sqrt(self.hd))
             native.linear(stt.o, w(pre + "cross_out.weight"), stt.y, bias=st.p(pre + "cross_out.bias"))
             native.layernorm_fwd(stt.x1, st.p(pre + "norm2.weight"), st.p(pre + "norm2.bias"), 1e-5, stt.x2, r=stt.y)
             native.linear(stt.x2, w(pre + "linear1.weight"), stt.h, bias=st.p(pre + "linear1.bias"),
                           act=native.ACT_RELU)
             native.linear(stt.h, w(pre + "linear2.weight"), stt.y, bias=st.p(pre + "linear2.bias"))
             native.layernorm_fwd(stt.x2, st.p(pre + "norm3.weight"), st.p(pre + "norm3.bias"), 1e-5, x, r=stt.y)
-        native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
-        native.greedy_pick(stt.logits, stt.ids, stt.pos, stt.end_id, self.pad_idx, stt.finished, stt.n_finished, V=V)
-        native.step_inc(stt.pos)
+        return x
 
     def _decode_step_fused(self, stt: "DecodeState"):
         """decode_step on bf16 with 8 GEMM/attention launches per layer (was 12): every post-LN residual
@@ -763,9 +830,19 @@ class TransformerDecoder:
         GEMM's operand staging / residual epilogue); the self-attention K|V row goes straight from the
         in_proj GEMM into the cache; the vocabulary head leaves each row's argmax as a packed atomic max
         (no logits in HBM) and the pick reads it and advances the position."""
-        d, H, L, V = self.d, self.H, self.L, self.V
-        st, w, p = self.store, self.store.w, self.store.p
-        B, S, Tm = stt.B, stt.S, stt.max_len
+        x = self._step_body_fused(stt)
+        w, p, V = self.store.w, self.store.p, self.V
+        # the head on the 128x128 GEMM with the argmax epilogue (mit_gemm argmax_keys): one round of 158 blocks,
+        # ~10 us, against ~20 us for mit_decode_gemm's 628 split-K 64x64 blocks at one per CU
+        # (per token step, 3 interleaved processes on one box: 667 -> 658 us, 383.7 k -> 389.0 k tokens/s)
+        native.gemm(x, w("fc_out.weight")[:V], None, stt.B, V, self.d, bias=p("fc_out.bias")[:V], argmax_keys=stt.keys)
+        native.greedy_pick_keys(stt.keys, stt.ids, stt.pos, stt.end_id, self.pad_idx, stt.finished, stt.n_finished)
+
+    def _step_body_fused(self, stt: "DecodeState") -> torch.Tensor:
+        """The fused bf16 token step up to the vocabulary head's operand: LN3 of the last layer in bf16 [B, d]."""
+        d, L = self.d, self.L
+        w, p = self.store.w, self.store.p
+        Tm = stt.max_len
         z1, z2, z3 = stt.z
         s1, s2, s3 = stt.zst
         scale = 1.0 / math.sqrt(self.hd)
@@ -782,15 +859,11 @@ class TransformerDecoder:
             ln2 = (s2, p(pre + "norm2.weight"), p(pre + "norm2.bias"))
             native.decode_gemm(a, w(pre + "self_in.weight"), out=stt.qkv, bias=p(pre + "self_in.bias"), a_ln=a_ln,
                                cache=cache, c_row=2 * d, c_batch=Tm * 2 * d, kv_col0=d, pos=stt.pos)
-            native.attention_decode(stt.qkv, 3 * d, cache, 2 * d, Tm * 2 * d, cache[:, :, d:], 2 * d, Tm * 2 * d, stt.o,
-                                    d, B, H, pos=stt.pos, key_tokens=stt.ids, tok_batch=Tm, pad_idx=self.pad_idx,
-                                    scale=scale, Dh=self.hd)
+            self._attn_self(stt, cache, scale)
             native.decode_gemm(stt.o, w(pre + "self_out.weight"), bias=p(pre + "self_out.bias"), residual=a, r_ln=a_ln,
                                z_out=z1, stats_out=s1)
             native.decode_gemm(z1, w(pre + "cross_q.weight"), out=stt.q, bias=p(pre + "cross_q.bias"), a_ln=ln1)
-            kvl = stt.kv[l]
-            native.attention_decode(stt.q, d, kvl, 2 * d, S * 2 * d, kvl[:, d:], 2 * d, S * 2 * d,
-                                    stt.o, d, B, H, Lk=S, scale=scale, Dh=self.hd)
+            self._attn_cross(stt, stt.kv[l], scale)
             native.decode_gemm(stt.o, w(pre + "cross_out.weight"), bias=p(pre + "cross_out.bias"), residual=z1,
                                r_ln=ln1, z_out=z2, stats_out=s2)
             native.decode_gemm(z2, w(pre + "linear1.weight"), out=stt.h, bias=p(pre + "linear1.bias"),
@@ -799,11 +872,38 @@ class TransformerDecoder:
                                z_out=z3, stats_out=s3)
         q3 = f"layers.{L - 1}.norm3."
         native.decode_layernorm(z3, s3, p(q3 + "weight"), p(q3 + "bias"), stt.x)
-        # the head on the 128x128 GEMM with the argmax epilogue (mit_gemm argmax_keys): one round of 158 blocks,
-        # ~10 us, against ~20 us for mit_decode_gemm's 628 split-K 64x64 blocks at one per CU
-        # (per token step, 3 interleaved processes on one box: 667 -> 658 us, 383.7 k -> 389.0 k tokens/s)
-        native.gemm(stt.x, w("fc_out.weight")[:V], None, B, V, d, bias=p("fc_out.bias")[:V], argmax_keys=stt.keys)
-        native.greedy_pick_keys(stt.keys, stt.ids, stt.pos, stt.end_id, self.pad_idx, stt.finished, stt.n_finished)
+        return stt.x
+
+    # --- beam search on the same step (csrc/beam.hip) ---------------------------------------------------
+    def beam_begin(self, mem: torch.Tensor, mem_ld: int, S: int, B: int, K: int, max_len: int, start_id: int,
+                   end_id: int) -> "BeamState":
+        """Set up a beam search of K slots per image over B images (memory rows mem [B*S, d], row stride
+        mem_ld): the cross-attention K/V of every layer computed once per IMAGE (its K beams share it), empty
+        slot-ordered self-attention caches for the B*K rows, START in every slot, score 0 in slot 0 and -inf in
+        the others, position 0 on the device."""
+        if max_len > self.pe.shape[0]:
+            raise ValueError(f"max_len {max_len} exceeds the positional table ({self.pe.shape[0]} = "
+                             f"decoder_max_seq_len; the reference's PositionalEncoding would fail too)")
+        if not 1 <= K <= 8 or K > self.V:
+            raise ValueError(f"beam_size {K} must be in 1..8 and at most the vocabulary ({self.V})")
+        if max_len < 2:
+            raise ValueError("beam search needs max_len >= 2")
+        stt = BeamState(self, B, K, S, max_len, start_id, end_id)
+        d, L, st = self.d, self.L, self.store
+        wkv, bkv = st.w("cross_kv.weight"), st.p("cross_kv.bias")
+        for l in range(L):
+            native.gemm(mem, wkv[l * 2 * d:], stt.kv[l], B * S, 2 * d, d, lda=mem_ld, bias=bkv[l * 2 * d:])
+        return stt
+
+    def beam_step(self, stt: "BeamState"):
+        """One token for every beam: the greedy step's body with the ancestry-gathered attention, the head as a
+        plain GEMM into f32 logits [B*K, padded_vocab], then the selection (which advances the position).
+        No host synchronisation: recordable and capturable like decode_step."""
+        x = self._step_body_fused(stt) if stt.fused else self._step_body(stt)
+        st, w = self.store, self.store.w
+        native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
+        native.beam_select(stt.logits, self.V, stt.score, stt.ids, stt.anc, stt.pos, stt.end_id, self.pad_idx,
+                           stt.finished, stt.length, stt.n_finished, stt.ws, stt.images, stt.K)
 
     def forward_ops(self, tokens: torch.Tensor, mem: torch.Tensor, S: int, params: Dict[str, torch.Tensor],
                     seed: Optional[torch.Tensor], drop_p: float, mem_keys: Optional[torch.Tensor] = None) -> torch.Tensor:

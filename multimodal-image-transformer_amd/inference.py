@@ -60,10 +60,13 @@ def load_model(checkpoint_path: str, vocab_size: Optional[int] = None, device=No
 
 def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]] = None,
                       start_token_id: int = config.START_TOKEN_ID, end_token_id: int = config.END_TOKEN_ID,
-                      max_len: int = config.MAX_SEQ_LEN, batch_size: int = 256):
+                      max_len: int = config.MAX_SEQ_LEN, batch_size: int = 256, beam_size: Optional[int] = None,
+                      length_penalty: float = 0.0):
     """Captions for a list of PIL images / HWC arrays or a [B,3,H,W] pixel tensor, `batch_size` images
     per batched decode. Returns [(processed ids, text)] — text is None without a `decode` function
-    (the BPE tokenizer, tokenizer.py, is a host-side library outside this path)."""
+    (the BPE tokenizer, tokenizer.py, is a host-side library outside this path).
+    beam_size: None decodes greedily (generate_batch); a number decodes with that many beams per image
+    (generate_beam_batch, ranked by score / length**length_penalty) and post-processes the best beam alike."""
     if isinstance(images, torch.Tensor):
         pv = images if images.dim() == 4 else images.unsqueeze(0)
     else:
@@ -79,7 +82,11 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
     chunk = dev(starts[0]) if starts else None
     for j in range(len(starts)):
         nxt = dev(starts[j + 1]) if j + 1 < len(starts) else None
-        ids = model.generate_batch(chunk, start_token_id, end_token_id, max_len=max_len, next_images=nxt)
+        if beam_size is None:
+            ids = model.generate_batch(chunk, start_token_id, end_token_id, max_len=max_len, next_images=nxt)
+        else:
+            ids = model.generate_beam_batch(chunk, start_token_id, end_token_id, max_len=max_len,
+                                            beam_size=beam_size, length_penalty=length_penalty)
         chunk = nxt
         for seq in ids:
             p = postprocess_ids(seq, start_token_id, end_token_id)

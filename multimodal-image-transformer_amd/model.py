@@ -65,6 +65,19 @@ class GraphedStep:
         return self.loss
 
 
+def rank_beams(ids: List[List[int]], scores: List[float], lengths: List[int], K: int, length_penalty: float = 0.0,
+               return_all: bool = False):
+    """Final ranking of a beam search (host): rows are image-major, slot-minor; per image the slots sorted by
+    score / length**length_penalty, best first, ties to the lower slot. Returns per image the best ids, or with
+    return_all the K (ids, score) pairs in rank order."""
+    out = []
+    for b in range(len(ids) // K):
+        rows = range(b * K, (b + 1) * K)
+        order = sorted(rows, key=lambda r: (-(scores[r] / max(lengths[r], 1) ** length_penalty), r))
+        out.append([(ids[r], scores[r]) for r in order] if return_all else ids[order[0]])
+    return out
+
+
 class ImageToTextModel:
     def __init__(self, decoder_vocab_size: int, decoder_embed_dim: int, decoder_heads: int, decoder_layers: int,
                  decoder_ff_dim: int, decoder_max_seq_len: int, decoder_dropout: float, decoder_pad_idx: int, *,
@@ -555,6 +568,66 @@ class ImageToTextModel:
         for stt in states:
             out.extend(stt.token_lists())
         return out
+
+    @torch.no_grad()
+    def generate_beam_batch(self, images, start_token_id: int, end_token_id: int, max_len: int = 100,
+                            beam_size: int = config.BEAM_SIZE, length_penalty: float = 0.0, return_all: bool = False,
+                            use_graph: bool = True, check_every: int = 8):
+        """Beam-search captions for a whole batch: beam_size slots per image on the KV-cache step of
+        generate_batch (decoder.beam_begin / beam_step). Per step a live beam offers its V continuations at
+        score + log_softmax(logits), a finished beam itself once (padded); the beam_size best by (score, lower
+        parent, lower token) go on; decoding stops when every beam of every image is finished, or at max_len.
+        The selection, the KV-cache ancestry and every index stay on the device, so a step is recorded / captured
+        and replayed as in generate_batch (same launch choices: use_graph, env MIT_DECODE_LAUNCH); the host reads
+        the finished count every `check_every` tokens.
+
+        Beams are ranked on the host by score / length**length_penalty (length: generated tokens, END included;
+        0.0 ranks by the raw log-probability), ties to the lower slot. Returns per image the best beam's ids
+        (START .. first END inclusive, else max_len ids), or with return_all its beam_size (ids, score) pairs,
+        best first."""
+        self.eval()
+        pv = images if isinstance(images, torch.Tensor) else \
+            self.image_processor(images=images, return_tensors="pt")["pixel_values"]
+        pv = pv.to(self.device).float()
+        B, K = pv.shape[0], int(beam_size)
+        mem, mem_ld, S, _, _ = self._encode_memory(pv)
+        dec = self.decoder
+        stt = dec.beam_begin(mem, mem_ld, S, B, K, max_len, start_token_id, end_token_id)
+        steps = max_len - 1
+        dec.beam_step(stt)  # position 0 (eager: warms every kernel before capture)
+        done = 1
+        launch = os.environ.get("MIT_DECODE_LAUNCH", "plan") if use_graph else "eager"
+        if launch == "graph" and steps > 1:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                dec.beam_step(stt)
+            run = graph.replay
+        elif launch == "plan" and steps > 1:
+            prog = native.record(lambda: dec.beam_step(stt))
+            done += 1
+            run = prog.run
+        else:
+            run = lambda: dec.beam_step(stt)  # noqa: E731
+        while done < steps:
+            n = min(check_every, steps - done)
+            for _ in range(n):
+                run()
+            done += n
+            if int(stt.n_finished.item()) == B * K:
+                break
+        return rank_beams(stt.token_lists(), stt.score.cpu().tolist(), stt.length.cpu().tolist(), K, length_penalty,
+                          return_all)
+
+    @torch.no_grad()
+    def generate_beam(self, image, start_token_id: int, end_token_id: int, max_len: int = 100,
+                      beam_size: int = config.BEAM_SIZE, length_penalty: float = 0.0, return_all: bool = False):
+        """generate_beam_batch for one image (a PIL image / HWC array or a [3,H,W] / [1,3,H,W] pixel tensor)."""
+        if isinstance(image, torch.Tensor):
+            pv = image if image.dim() == 4 else image.unsqueeze(0)
+        else:
+            pv = self.image_processor(images=image, return_tensors="pt")["pixel_values"]
+        return self.generate_beam_batch(pv, start_token_id, end_token_id, max_len=max_len, beam_size=beam_size,
+                                        length_penalty=length_penalty, return_all=return_all)[0]
 
     def sync_shadow(self):
         """Re-cast the bf16 weight shadow the kernels read from the f32 master. Needed only after

@@ -175,6 +175,11 @@ SIGNATURES = {
     "mit_greedy_pick_keys": (I, [L, vp, vp, L, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp]),
     "mit_decode_gemm": (I, [ctypes.POINTER(DecodeGemmArgs), vp]),
     "mit_decode_layernorm": (I, [L, L, vp, L, vp, vp, vp, Fl, vp, L, vp]),
+    "mit_attention_decode_beam": (I, [I, L, L, L, vp, L, vp, L, L, vp, L, L, vp, L, L, vp, L, vp, L, vp, L, I, Fl, vp]),
+    "mit_attention_decode_beam_plan": (I, [I, L, L, L, vp, L, vp, L, L, vp, L, L, vp, L, L, vp, L, vp, L, vp]),
+    "mit_beam_select_ws_bytes": (L, [L, L, L]),
+    "mit_beam_select": (I, [L, L, L, vp, L, vp, vp, L, vp, L, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, L,
+                            vp]),
 }
 
 
@@ -907,6 +912,39 @@ def decode_layernorm(z, stats, gamma, beta, out, eps=1e-5):
     M, W = z.shape
     _check(lib().mit_decode_layernorm(M, W, ptr(z), z.stride(0), ptr(stats), ptr(gamma), ptr(beta), eps, ptr(out),
                                       out.stride(0), stream_ptr()), "mit_decode_layernorm")
+
+
+# --- beam-search decoding (beam.hip) ---------------------------------------------------------------
+def attention_decode_beam(q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, R, H, *, Lk=0, pos=None,
+                          group=1, anc=None, key_tokens=None, tok_batch=0, pad_idx=0, scale=0.125, Dh=64):
+    """attention_decode over R = B * group rows whose K / V / token batch is looked up per key: through the
+    ancestor table anc (int32 [R, ld]: batch (r // group) * group + anc[r, j]) or, without one, r // group (the
+    beams of an image share one cross-attention K / V)."""
+    _check(lib().mit_attention_decode_beam(dtype_code(q), R, H, Dh, ptr(q), q_batch, ptr(k), k_row, k_batch, ptr(v),
+                                           v_row, v_batch, ptr(o), o_batch, Lk, ptr(pos), group, ptr(anc),
+                                           anc.stride(0) if anc is not None else 0, ptr(key_tokens), tok_batch,
+                                           pad_idx, scale, stream_ptr()), "mit_attention_decode_beam")
+
+
+def attention_decode_beam_plan(dtype, R, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, *, Lk=0,
+                               pos=None, group=1, anc=None, ld_anc=0, key_tokens=None) -> int:
+    """The kernel family (DECODE_ATTN_*) attention_decode_beam would launch (host only, no GPU needed); -1 for
+    rejected arguments. Pointers are integers (addresses) or None."""
+    return lib().mit_attention_decode_beam_plan(dtype, R, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o,
+                                                o_batch, Lk, pos, group, anc, ld_anc, key_tokens)
+
+
+def beam_select_ws_bytes(B, K, V) -> int:
+    return lib().mit_beam_select_ws_bytes(B, K, V)
+
+
+def beam_select(logits, V, score, tok, anc, pos, end_id, pad_id, finished, length, n_finished, ws, B, K):
+    """One beam selection step at the device position pos (mit_beam_select): the K best continuations of each of
+    the B images from f32 logits [B*K, ld], the new slot states, tok[:, pos+1], the ancestor table; pos += 1."""
+    _check(lib().mit_beam_select(B, K, V, ptr(logits), logits.stride(0), ptr(score), ptr(tok), tok.stride(0), ptr(anc),
+                                 anc.stride(0), ptr(pos), int(end_id), int(pad_id), ptr(finished), ptr(length),
+                                 ptr(n_finished), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
+           "mit_beam_select")
 
 
 def image_normalize(src_u8, dst, mean, std):
