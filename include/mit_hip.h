@@ -593,6 +593,46 @@ int mit_beam_select(long B, long K, long V, const float* logits, long ld, float*
                     int* n_finished, void* ws, long ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sampled decoding on the same KV-cache step (csrc/sample.hip): one token per row drawn from the row's
+ * temperature / top-k / top-p filtered distribution, everything the step indexes with in device memory.
+ *
+ * sample_uniform (the debug export, as mit_dropout_mask is for dropout): out[r] = u(r) for r < R, the uniform
+ *   mit_sample_pick draws with at position p = *pos. The rule (csrc/sample.hip, lowbias32 as below under
+ *   Utilities), all arithmetic modulo 2^32 unless said:
+ *     key = (seed ? *seed : 0) ^ (0xD6E8FEB86659FD93 * (MIT_SAMPLE_SITE + 1) mod 2^64)
+ *     a = lowbias32(lo32(key) + 0x9E3779B9);  b = lowbias32(hi32(key) ^ a)
+ *     h = lowbias32(lowbias32((u32)(row0 + r) ^ a) ^ (u32)p ^ b);  u = (h >> 8) * 2^-24, in [0, 1)
+ *   row0 is the global index of row 0: a row's stream depends on its global index, not on how a batch was cut.
+ * sample_pick: for a live row r at p = *pos, with l_v = logits[r*ld + v], v < V (columns >= V are never read):
+ *   - order: logit descending, then token ascending (integer compares on order-preserving keys; -0.0 == +0.0);
+ *   - K1 = the first top_k tokens of the order (top_k == 0 or >= V: all of them; boundary ties go by the order);
+ *   - w_v = exp((l_v - m) / temperature), m the row maximum; Z1 = sum of w over K1;
+ *   - K2 = the shortest prefix of the order inside K1 whose weight reaches top_p * Z1, one token at least
+ *     (top_p >= 1: K2 = K1);
+ *   - u = uniforms ? uniforms[r] : the hash above; Z2 = sum of w over K2; the pick is the first token of K2 in
+ *     ASCENDING TOKEN order whose running sum exceeds u * Z2, or the largest token of K2 when rounding leaves none;
+ *   - ids[r*ld_ids + p + 1] = token; logprob[r] += l_token - lse(l) (logprob != NULL; lse over the unfiltered row
+ *     at temperature 1, m + log(sum exp(l - m)) in f32 as mit_beam_select); length[r] += 1 (length != NULL);
+ *     token == end_id: finished[r] = 1 and *n_finished += 1 (atomic).
+ *   A finished row gets pad_id in that column; its logits row is never read (it may hold NaN) and nothing else
+ *   of it is written. *pos = p + 1, written once by the last block to take `ticket` (int32, 0 before and after:
+ *   mit_greedy_pick_advance's protocol); every block reads *pos before it takes its ticket. ids columns other
+ *   than p + 1 are not written (a step at p + 1 >= ld_ids writes no token). A row holding a NaN, or whose maximum
+ *   is -inf: the pick is undefined but lies in [0, V), and nothing outside the above is written.
+ *   temperature > 0, top_p > 0, top_k >= 0, 1 <= V < 2^31, ld >= V, ld_ids >= 2, 0 <= R < 2^31, logits 4-B aligned
+ *   (16-B loads when ld % 4 == 0 and logits is 16-B aligned: the same result); logits, ids, pos, finished,
+ *   n_finished and ticket not NULL; seed (NULL: 0) and uniforms may be NULL, uniforms wins. R == 0 launches
+ *   nothing. Arguments are checked before anything is recorded or launched. Asynchronous, recordable, capturable.
+ *   Deterministic: the sets are decided by integer compares, every float sum runs in a fixed order and there are
+ *   no float atomics, so a second launch on the same inputs is bitwise equal. */
+#define MIT_SAMPLE_SITE 9000u
+int mit_sample_uniform(long R, long row0, const uint64_t* seed, const int64_t* pos, float* out, void* stream);
+int mit_sample_pick(long R, long V, const float* logits, long ld, float temperature, long top_k, float top_p,
+                    const uint64_t* seed, long row0, const float* uniforms, int64_t* ids, long ld_ids, int64_t* pos,
+                    int64_t end_id, int64_t pad_id, int* finished, int* n_finished, float* logprob, int* length,
+                    int* ticket, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Utilities. cast: f32 -> operand dtype copy (weights to the bf16 shadow); fill f32.
  * dropout_mask_debug: writes the keep-multiplier (0 or 1/(1-p)) the kernels use at
  * (seed, site, idx) for idx in [0, n) — tests rebuild reference masks from it.

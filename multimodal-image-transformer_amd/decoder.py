@@ -260,6 +260,7 @@ class DecodeState:
     caches [B, max_len, 2d] (K | V), and the B-row activations of one token step."""
 
     K = 0  # beam slots per image (BeamState); 0: greedy rows
+    group = 1  # rows that share one cross-attention memory (SampleState: the samples of an image)
 
     def __init__(self, dec: "TransformerDecoder", B: int, S: int, max_len: int, start_id: int, end_id: int,
                  images: Optional[int] = None):
@@ -335,6 +336,27 @@ class BeamState(DecodeState):
                 row = row[: row.index(self.end_id, 1) + 1]
             out.append(row)
         return out
+
+
+class SampleState(DecodeState):
+    """Device state of a sampled decode (TransformerDecoder.sample_begin / sample_step): a DecodeState of
+    R = images * N rows (row b*N + n is sample n of image b), each with its own self-attention cache, plus per
+    row the cumulative log-probability `logprob` (f32, at temperature 1 over the unfiltered vocabulary) and
+    `length` (generated tokens, END included), the device seed, the global index `row0` of row 0 and the filter
+    settings. The cross-attention K/V holds one memory per image, read by its N samples (group = N)."""
+
+    def __init__(self, dec: "TransformerDecoder", images: int, N: int, S: int, max_len: int, start_id: int,
+                 end_id: int, temperature: float, top_k: int, top_p: float, seed: int, row0: int):
+        super().__init__(dec, images * N, S, max_len, start_id, end_id, images=images)
+        dev = dec.device
+        self.images, self.group = images, N
+        self.temperature, self.top_k, self.top_p, self.row0 = float(temperature), int(top_k), float(top_p), int(row0)
+        self.logprob = torch.zeros(images * N, dtype=torch.float32, device=dev)
+        self.length = torch.zeros(images * N, dtype=torch.int32, device=dev)
+        s = int(seed) & 0xFFFFFFFFFFFFFFFF  # the kernels read a uint64
+        self.seed = torch.tensor([s - (1 << 64) if s >= (1 << 63) else s], dtype=torch.int64, device=dev)
+        if not hasattr(self, "ticket"):  # the fused state has one already
+            self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
 
 
 class TransformerDecoder:
@@ -791,9 +813,9 @@ class TransformerDecoder:
         """The step's cross-attention of stt.q over the image memory's K | V rows kvl -> stt.o; the K beams of an
         image share its one K/V."""
         d, S = self.d, stt.S
-        if stt.K:
+        if stt.K or stt.group > 1:  # the slots (beam) or samples of an image read its one K/V
             native.attention_decode_beam(stt.q, d, kvl, 2 * d, S * 2 * d, kvl[:, d:], 2 * d, S * 2 * d, stt.o, d, stt.B,
-                                         self.H, Lk=S, group=stt.K, scale=scale, Dh=self.hd)
+                                         self.H, Lk=S, group=stt.K or stt.group, scale=scale, Dh=self.hd)
         else:
             native.attention_decode(stt.q, d, kvl, 2 * d, S * 2 * d, kvl[:, d:], 2 * d, S * 2 * d,
                                     stt.o, d, stt.B, self.H, Lk=S, scale=scale, Dh=self.hd)
@@ -904,6 +926,43 @@ class TransformerDecoder:
         native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
         native.beam_select(stt.logits, self.V, stt.score, stt.ids, stt.anc, stt.pos, stt.end_id, self.pad_idx,
                            stt.finished, stt.length, stt.n_finished, stt.ws, stt.images, stt.K)
+
+    # --- sampling on the same step (csrc/sample.hip) ------------------------------------------------------
+    def sample_begin(self, mem: torch.Tensor, mem_ld: int, S: int, B: int, N: int, max_len: int, start_id: int,
+                     end_id: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                     row0: int = 0) -> "SampleState":
+        """Set up a sampled decode of N samples per image over B images (memory rows mem [B*S, d], row stride
+        mem_ld): the cross-attention K/V of every layer computed once per IMAGE, an empty self-attention cache per
+        row, START in every row, log-probability 0, position 0 on the device. Row r draws with the uniform of
+        (seed, row0 + r, position)."""
+        if max_len > self.pe.shape[0]:
+            raise ValueError(f"max_len {max_len} exceeds the positional table ({self.pe.shape[0]} = "
+                             f"decoder_max_seq_len; the reference's PositionalEncoding would fail too)")
+        if max_len < 2:
+            raise ValueError("sampling needs max_len >= 2")
+        if N < 1:
+            raise ValueError(f"num_samples {N} must be at least 1")
+        if not temperature > 0 or not top_p > 0 or top_k < 0:
+            raise ValueError(f"sampling needs temperature > 0, top_p > 0 and top_k >= 0 (got {temperature}, {top_p}, "
+                             f"{top_k})")
+        stt = SampleState(self, B, N, S, max_len, start_id, end_id, temperature, top_k, top_p, seed, row0)
+        d, L, st = self.d, self.L, self.store
+        wkv, bkv = st.w("cross_kv.weight"), st.p("cross_kv.bias")
+        for l in range(L):
+            native.gemm(mem, wkv[l * 2 * d:], stt.kv[l], B * S, 2 * d, d, lda=mem_ld, bias=bkv[l * 2 * d:])
+        return stt
+
+    def sample_step(self, stt: "SampleState"):
+        """One sampled token for every row: the greedy step's body (each row attends over its own cache, the N
+        samples of an image over its one cross-attention K/V), the head as a plain GEMM into f32 logits
+        [B*N, padded_vocab], then the pick (which advances the position). No host synchronisation: recordable
+        and capturable like decode_step."""
+        x = self._step_body_fused(stt) if stt.fused else self._step_body(stt)
+        st, w = self.store, self.store.w
+        native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
+        native.sample_pick(stt.logits, self.V, stt.temperature, stt.top_k, stt.top_p, stt.seed, stt.row0, None, stt.ids,
+                           stt.pos, stt.end_id, self.pad_idx, stt.finished, stt.n_finished, stt.logprob, stt.length,
+                           stt.ticket)
 
     def forward_ops(self, tokens: torch.Tensor, mem: torch.Tensor, S: int, params: Dict[str, torch.Tensor],
                     seed: Optional[torch.Tensor], drop_p: float, mem_keys: Optional[torch.Tensor] = None) -> torch.Tensor:

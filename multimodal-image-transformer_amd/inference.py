@@ -61,12 +61,18 @@ def load_model(checkpoint_path: str, vocab_size: Optional[int] = None, device=No
 def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]] = None,
                       start_token_id: int = config.START_TOKEN_ID, end_token_id: int = config.END_TOKEN_ID,
                       max_len: int = config.MAX_SEQ_LEN, batch_size: int = 256, beam_size: Optional[int] = None,
-                      length_penalty: float = 0.0):
+                      length_penalty: float = 0.0, temperature: Optional[float] = None, top_k: int = 0,
+                      top_p: float = 1.0, seed: int = 0):
     """Captions for a list of PIL images / HWC arrays or a [B,3,H,W] pixel tensor, `batch_size` images
     per batched decode. Returns [(processed ids, text)] — text is None without a `decode` function
     (the BPE tokenizer, tokenizer.py, is a host-side library outside this path).
     beam_size: None decodes greedily (generate_batch); a number decodes with that many beams per image
-    (generate_beam_batch, ranked by score / length**length_penalty) and post-processes the best beam alike."""
+    (generate_beam_batch, ranked by score / length**length_penalty) and post-processes the best beam alike.
+    temperature: a number draws each caption from the model's distribution instead (generate_sample_batch with
+    top_k / top_p / seed; one sample per image). Image i of `images` draws with (seed, i) whatever the
+    batch_size, so the captions do not depend on how the images are batched."""
+    if temperature is not None and beam_size is not None:
+        raise ValueError("generate_captions: choose beam search (beam_size) or sampling (temperature), not both")
     if isinstance(images, torch.Tensor):
         pv = images if images.dim() == 4 else images.unsqueeze(0)
     else:
@@ -82,7 +88,11 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
     chunk = dev(starts[0]) if starts else None
     for j in range(len(starts)):
         nxt = dev(starts[j + 1]) if j + 1 < len(starts) else None
-        if beam_size is None:
+        if temperature is not None:
+            ids = model.generate_sample_batch(chunk, start_token_id, end_token_id, max_len=max_len,
+                                              temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                              image_offset=starts[j])
+        elif beam_size is None:
             ids = model.generate_batch(chunk, start_token_id, end_token_id, max_len=max_len, next_images=nxt)
         else:
             ids = model.generate_beam_batch(chunk, start_token_id, end_token_id, max_len=max_len,
@@ -115,12 +125,33 @@ def _tokenizer_decode():
     return lambda ids: tok.decode(ids, skip_special_tokens=False)
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Generate captions for images with a trained checkpoint.")
     ap.add_argument("--image_path", nargs="+", required=True, help="one or more image files")
     ap.add_argument("--checkpoint_path", required=True, help=".safetensors or .pt checkpoint")
     ap.add_argument("--batch_size", type=int, default=256)
+    ap.add_argument("--beam_size", type=int, default=None, help="beam search with this many beams per image")
+    ap.add_argument("--length_penalty", type=float, default=0.0,
+                    help="beams are ranked by score / length**length_penalty")
+    ap.add_argument("--temperature", type=float, default=None,
+                    help="sample each caption at this temperature instead of decoding greedily")
+    ap.add_argument("--top_k", type=int, default=0, help="sampling: keep the k most likely tokens (0: all)")
+    ap.add_argument("--top_p", type=float, default=1.0, help="sampling: keep the smallest set of this mass (1: all)")
+    ap.add_argument("--seed", type=int, default=0, help="sampling seed")
+    return ap
+
+
+def decode_options(args) -> dict:
+    """The parsed command line as generate_captions keyword arguments."""
+    return dict(batch_size=args.batch_size, beam_size=args.beam_size, length_penalty=args.length_penalty,
+                temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if args.temperature is not None and args.beam_size is not None:
+        ap.error("--beam_size and --temperature exclude each other")
     from PIL import Image
     model = load_model(args.checkpoint_path)
     for p in args.image_path:
@@ -128,7 +159,7 @@ def main(argv=None):
             raise FileNotFoundError(f"Image file not found: {p}")
     ims = [Image.open(p).convert("RGB") for p in args.image_path]
     for p, (ids, text) in zip(args.image_path, generate_captions(model, ims, _tokenizer_decode(),
-                                                                  batch_size=args.batch_size)):
+                                                                  **decode_options(args))):
         print(f"{p}: {text if text is not None else ids}")
 
 

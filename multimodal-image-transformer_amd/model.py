@@ -629,6 +629,71 @@ class ImageToTextModel:
         return self.generate_beam_batch(pv, start_token_id, end_token_id, max_len=max_len, beam_size=beam_size,
                                         length_penalty=length_penalty, return_all=return_all)[0]
 
+    @torch.no_grad()
+    def generate_sample_batch(self, images, start_token_id: int, end_token_id: int, max_len: int = 100,
+                              temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_samples: int = 1,
+                              seed: int = 0, image_offset: int = 0, return_logprob: bool = False,
+                              use_graph: bool = True, check_every: int = 8):
+        """Sampled captions for a whole batch: num_samples rows per image on the KV-cache step of generate_batch
+        (decoder.sample_begin / sample_step). Per step a live row draws its next token from softmax(logits /
+        temperature) restricted to the top_k most likely tokens and, inside them, to the shortest prefix of mass
+        top_p (0 / 1.0: filter off); a row stops after END, decoding when every row has, or at max_len. The draw
+        of sample n of image b at position p is a counter hash of (seed, (image_offset + b) * num_samples + n, p):
+        a caption depends on the seed and the image's global index, not on how the images were batched. The pick
+        and every index stay on the device, so a step is recorded / captured and replayed as in generate_batch
+        (same launch choices: use_graph, env MIT_DECODE_LAUNCH); the host reads the finished count every
+        `check_every` tokens.
+
+        Returns per image its ids (START .. first END inclusive, else max_len ids) when num_samples == 1 and
+        return_logprob is False; else per image its num_samples (ids, logprob) pairs, logprob being the sum of
+        log_softmax(logits)[token] (temperature 1, unfiltered) over the generated tokens, END included."""
+        self.eval()
+        pv = images if isinstance(images, torch.Tensor) else \
+            self.image_processor(images=images, return_tensors="pt")["pixel_values"]
+        pv = pv.to(self.device).float()
+        B, N = pv.shape[0], int(num_samples)
+        mem, mem_ld, S, _, _ = self._encode_memory(pv)
+        dec = self.decoder
+        stt = dec.sample_begin(mem, mem_ld, S, B, N, max_len, start_token_id, end_token_id, temperature=temperature,
+                               top_k=top_k, top_p=top_p, seed=seed, row0=int(image_offset) * N)
+        steps = max_len - 1
+        dec.sample_step(stt)  # position 0 (eager: warms every kernel before capture)
+        done = 1
+        launch = os.environ.get("MIT_DECODE_LAUNCH", "plan") if use_graph else "eager"
+        if launch == "graph" and steps > 1:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                dec.sample_step(stt)
+            run = graph.replay
+        elif launch == "plan" and steps > 1:
+            prog = native.record(lambda: dec.sample_step(stt))
+            done += 1
+            run = prog.run
+        else:
+            run = lambda: dec.sample_step(stt)  # noqa: E731
+        while done < steps:
+            n = min(check_every, steps - done)
+            for _ in range(n):
+                run()
+            done += n
+            if int(stt.n_finished.item()) == B * N:
+                break
+        ids = stt.token_lists()
+        if N == 1 and not return_logprob:
+            return ids
+        lp = stt.logprob.cpu().tolist()
+        return [[(ids[b * N + n], lp[b * N + n]) for n in range(N)] for b in range(B)]
+
+    @torch.no_grad()
+    def generate_sample(self, image, start_token_id: int, end_token_id: int, max_len: int = 100, **kwargs):
+        """generate_sample_batch for one image (a PIL image / HWC array or a [3,H,W] / [1,3,H,W] pixel tensor);
+        keyword arguments as generate_sample_batch."""
+        if isinstance(image, torch.Tensor):
+            pv = image if image.dim() == 4 else image.unsqueeze(0)
+        else:
+            pv = self.image_processor(images=image, return_tensors="pt")["pixel_values"]
+        return self.generate_sample_batch(pv, start_token_id, end_token_id, max_len=max_len, **kwargs)[0]
+
     def sync_shadow(self):
         """Re-cast the bf16 weight shadow the kernels read from the f32 master. Needed only after
         editing weights out of band (through ``p.data``, which torch's version counter does not see)

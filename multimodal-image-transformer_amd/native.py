@@ -180,6 +180,9 @@ SIGNATURES = {
     "mit_beam_select_ws_bytes": (L, [L, L, L]),
     "mit_beam_select": (I, [L, L, L, vp, L, vp, vp, L, vp, L, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp, L,
                             vp]),
+    "mit_sample_uniform": (I, [L, L, vp, vp, vp, vp]),
+    "mit_sample_pick": (I, [L, L, vp, L, Fl, L, Fl, vp, L, vp, vp, L, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp,
+                            vp, vp, vp]),
 }
 
 
@@ -945,6 +948,27 @@ def beam_select(logits, V, score, tok, anc, pos, end_id, pad_id, finished, lengt
                                  anc.stride(0), ptr(pos), int(end_id), int(pad_id), ptr(finished), ptr(length),
                                  ptr(n_finished), ptr(ws), ws.numel() * ws.element_size(), stream_ptr()),
            "mit_beam_select")
+
+
+# --- sampled decoding (sample.hip) ------------------------------------------------------------------
+SAMPLE_SITE = 9000  # MIT_SAMPLE_SITE
+
+
+def sample_uniform(R, row0, seed, pos, out):
+    """out[r] = the uniform sample_pick draws with for global row row0 + r at the device position pos
+    (mit_sample_uniform; seed: uint64-as-int64 device scalar or None)."""
+    _check(lib().mit_sample_uniform(R, row0, ptr(seed), ptr(pos), ptr(out), stream_ptr()), "mit_sample_uniform")
+
+
+def sample_pick(logits, V, temperature, top_k, top_p, seed, row0, uniforms, ids, pos, end_id, pad_id, finished,
+                n_finished, logprob, length, ticket):
+    """One sampled token per row at the device position pos (mit_sample_pick): temperature / top-k / top-p filter
+    of f32 logits [R, ld], the draw from `uniforms` (f32 [R]) or the (seed, row0 + r, pos) hash, ids[:, pos+1],
+    logprob += log-softmax of the pick, length += 1, the finished state; pos += 1 (`ticket`: int32 0)."""
+    _check(lib().mit_sample_pick(logits.shape[0], V, ptr(logits), logits.stride(0), float(temperature), int(top_k),
+                                 float(top_p), ptr(seed), int(row0), ptr(uniforms), ptr(ids), ids.stride(0), ptr(pos),
+                                 int(end_id), int(pad_id), ptr(finished), ptr(n_finished), ptr(logprob), ptr(length),
+                                 ptr(ticket), stream_ptr()), "mit_sample_pick")
 
 
 def image_normalize(src_u8, dst, mean, std):
