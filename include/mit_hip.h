@@ -633,6 +633,47 @@ int mit_sample_pick(long R, long V, const float* logits, long ld, float temperat
                     int* ticket, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Constrained decoding on the same KV-cache step (csrc/constrain.hip): a step's f32 logits rows edited in place
+ * between the vocabulary head and the pick (greedy_pick / greedy_pick_advance, beam_select, sample_pick). The
+ * picks treat the edited row as the model's logits: beam scores and sample log-probabilities are log_softmax of
+ * the CONSTRAINED row.
+ *
+ * logits_constrain: for a live row r at p = *pos the history is h[j], j = 0 .. p, START included:
+ *     anc == NULL: h[j] = tok[r*ld_tok + j]
+ *     anc != NULL: h[j] = tok[((r / group) * group + anc[r*ld_anc + j])*ld_tok + j]   (attention_decode_beam's
+ *                  key-token rule: a beam's constraints follow its ancestry; entries in [0, group))
+ *   Nothing at j > p is read. The row logits[r*ld .. r*ld + V) is edited in this order:
+ *   1. repetition penalty t = repetition_penalty (1: off): each DISTINCT token v of the history with 0 <= v < V
+ *      changes exactly once, not once per occurrence: l -> l * rinv if l > 0, else l * t, with rinv = 1.0f / t
+ *      computed once on the host in f32. One f32 multiply per case: -0.0, 0.0 and -inf take the l * t case;
+ *   2. no-repeat n-gram, n = no_repeat_ngram (0: off), when p + 1 >= n: with g = h[p-n+2 .. p] (the last n - 1
+ *      tokens, empty for n = 1), for every i in 0 .. p-n+1 with h[i .. i+n-2] == g the token h[i+n-1] becomes
+ *      -inf (n = 1 bans every token of the history);
+ *   3. minimum length: if p < min_length, end_id becomes -inf (END can first appear in column min_length + 1);
+ *   4. every token of `suppress` (device int64 [n_suppress]) becomes -inf;
+ *   5. forced token f = forced[r*ld_forced + p + 1] (device int64 [R, ld_forced], -1 = free), when forced != NULL,
+ *      p + 1 < ld_forced and 0 <= f < V: the whole row [0, V) becomes -inf except column f, which becomes 0.0f.
+ *      This overrides 1 to 4: any pick then takes f, and log_softmax of the row at f is exactly 0 (a prompt adds
+ *      nothing to a beam's score or a sample's log-probability).
+ *   A ban always wins over a penalty on the same token. History, suppress and end_id values outside [0, V) are
+ *   skipped: they never index the row (they still take part in the n-gram comparison). Columns >= V are never read
+ *   or written (the ld padding may hold NaN). Rows with finished[r] != 0 (finished may be NULL: every row live) are
+ *   neither read nor written (they may hold NaN). tok, anc, pos, finished, suppress and forced are not written. A
+ *   step at p < 0, p >= ld_tok or (anc != NULL) p >= ld_anc has no history column and leaves the rows as they are.
+ *   If every column of a row ends at -inf the later pick is undefined as in the pick contracts; its token stays in
+ *   [0, V). Outside a forced step p + 1 + n_suppress elements of a row are touched, not V.
+ *   logits, tok, pos not NULL; repetition_penalty > 0 and finite; no_repeat_ngram, min_length, n_suppress >= 0;
+ *   suppress not NULL when n_suppress > 0; 1 <= V < 2^31; ld >= V; 1 <= ld_tok <= 4096 (the history sits in LDS);
+ *   group >= 1; with anc: R % group == 0, ld_anc >= 1; with forced: ld_forced >= 1; logits 4-B aligned; 0 <= R <
+ *   2^31. Arguments are checked before anything is recorded or launched; R == 0 launches nothing. One kernel family
+ *   (one block per row), so there is no plan query. Asynchronous, recordable, capturable. Deterministic: no
+ *   atomics and no sums, a second launch from the same inputs is bitwise equal. */
+int mit_logits_constrain(long R, long V, float* logits, long ld, const int64_t* tok, long ld_tok, const int64_t* pos,
+                         long group, const int* anc, long ld_anc, const int* finished, float repetition_penalty,
+                         long no_repeat_ngram, long min_length, int64_t end_id, const int64_t* suppress,
+                         long n_suppress, const int64_t* forced, long ld_forced, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Utilities. cast: f32 -> operand dtype copy (weights to the bf16 shadow); fill f32.
  * dropout_mask_debug: writes the keep-multiplier (0 or 1/(1-p)) the kernels use at
  * (seed, site, idx) for idx in [0, n) — tests rebuild reference masks from it.

@@ -253,6 +253,78 @@ class _SideStream:
         self.pending.clear()
 
 
+class DecodeConstraints:
+    """What a token step may not pick (csrc/constrain.hip, mit_logits_constrain): edits of the step's f32 logits row
+    between the vocabulary head and the pick, the same for greedy, beam and sampled decoding. The picks treat the
+    edited row as the model's logits: beam scores and sample log-probabilities are log_softmax of the constrained row.
+
+      repetition_penalty  t > 0 (1: off): every distinct token of a row's history, START included, has its logit
+                          divided by t when positive, multiplied by t otherwise
+      no_repeat_ngram     n >= 0 (0: off): a token that would complete an n-gram the row already holds is banned
+      min_length          END is banned while fewer than min_length tokens have been generated
+      suppress            token ids that are never picked
+      prompts             None, one token list for every image, or one list per image (empty: no prompt): the
+                          tokens that follow START, forced at no cost in score or log-probability
+
+    All defaults: active() is False and every decode takes the unconstrained code path, launch for launch."""
+
+    def __init__(self, repetition_penalty: float = 1.0, no_repeat_ngram: int = 0, min_length: int = 0,
+                 suppress=(), prompts=None):
+        self.repetition_penalty = float(repetition_penalty)
+        self.no_repeat_ngram = int(no_repeat_ngram)
+        self.min_length = int(min_length)
+        self.suppress = tuple(int(t) for t in (suppress if suppress is not None else ()))
+        if prompts is not None:
+            prompts = list(prompts)
+            per_image = len(prompts) > 0 and all(isinstance(p, (list, tuple)) for p in prompts)
+            prompts = [[int(t) for t in p] for p in prompts] if per_image else [int(t) for t in prompts]
+        self.prompts = prompts
+
+    def per_image(self) -> bool:
+        return bool(self.prompts) and isinstance(self.prompts[0], list)
+
+    def has_prompts(self) -> bool:
+        return bool(self.prompts) and (not self.per_image() or any(self.prompts))
+
+    def active(self) -> bool:
+        return (self.repetition_penalty != 1.0 or self.no_repeat_ngram != 0 or self.min_length != 0
+                or bool(self.suppress) or self.has_prompts())
+
+    def image_prompts(self, B: int) -> List[List[int]]:
+        """One prompt (possibly empty) per image of a batch of B."""
+        if not self.prompts:
+            return [[] for _ in range(B)]
+        if not self.per_image():
+            return [list(self.prompts) for _ in range(B)]
+        if len(self.prompts) != B:
+            raise ValueError(f"prompts: {len(self.prompts)} lists for {B} images")
+        return [list(p) for p in self.prompts]
+
+    def rows(self, lo: int, hi: int) -> "DecodeConstraints":
+        """The constraints of images lo .. hi - 1 (generate_batch's row groups)."""
+        pr = self.prompts[lo:hi] if self.per_image() else self.prompts
+        return DecodeConstraints(self.repetition_penalty, self.no_repeat_ngram, self.min_length, self.suppress, pr)
+
+    def validate(self, V: int, max_len: int, end_id: int, B: int):
+        """Host checks against a vocabulary of V, a decode of B images to max_len ids and its END."""
+        t = self.repetition_penalty
+        if not (t > 0 and math.isfinite(t)):
+            raise ValueError(f"repetition_penalty {t} must be positive and finite")
+        if self.no_repeat_ngram < 0 or self.min_length < 0:
+            raise ValueError(f"no_repeat_ngram {self.no_repeat_ngram} and min_length {self.min_length} must be >= 0")
+        for v in self.suppress:
+            if not 0 <= v < V:
+                raise ValueError(f"suppress: token {v} outside the vocabulary [0, {V})")
+        for p in self.image_prompts(B):
+            if 1 + len(p) > max_len:
+                raise ValueError(f"prompt of {len(p)} tokens does not fit in max_len {max_len} after START")
+            for v in p:
+                if not 0 <= v < V:
+                    raise ValueError(f"prompt: token {v} outside the vocabulary [0, {V})")
+                if v == end_id:
+                    raise ValueError(f"prompt: contains END ({end_id})")
+
+
 class DecodeState:
     """Device state of a batched greedy decode (TransformerDecoder.decode_begin / decode_step):
     token ids [B, max_len] (int64; column 0 = START), the device position, per-row finished flags
@@ -261,6 +333,9 @@ class DecodeState:
 
     K = 0  # beam slots per image (BeamState); 0: greedy rows
     group = 1  # rows that share one cross-attention memory (SampleState: the samples of an image)
+    cons: Optional[DecodeConstraints] = None  # active constraints (TransformerDecoder._constrain_begin), else None
+    suppress: Optional[torch.Tensor] = None   # with cons: the suppressed ids on the device (int64), or None
+    forced: Optional[torch.Tensor] = None     # with cons: int64 [rows, Lp + 1], column j + 1 = prompt token j, -1 = free
 
     def __init__(self, dec: "TransformerDecoder", B: int, S: int, max_len: int, start_id: int, end_id: int,
                  images: Optional[int] = None):
@@ -768,15 +843,43 @@ class TransformerDecoder:
         side.run(lambda: native.gemm_grouped(probs, A.gws, ln_jobs=(j3, j2, j1)), reads=(dyF, dh, dyC, dq, dyS, dqkv))
 
     # --- batched greedy decoding with a KV cache (config 5) ---------------------------------------
+    def _constrain_begin(self, stt: "DecodeState", constraints: Optional[DecodeConstraints], images: int, rep: int):
+        """Attach active constraints to a fresh state of images * rep rows (rep: the beams / samples of an image):
+        validation on the host, the suppress list and the forced-token table on the device. Inactive or no
+        constraints leave the state as it is, and its steps make no constraint launch."""
+        if constraints is None or not constraints.active():
+            return
+        constraints.validate(self.V, stt.max_len, stt.end_id, images)
+        stt.cons = constraints
+        if constraints.suppress:
+            stt.suppress = torch.tensor(constraints.suppress, dtype=torch.int64, device=self.device)
+        if constraints.has_prompts():
+            prompts = constraints.image_prompts(images)
+            forced = torch.full((images, max(len(p) for p in prompts) + 1), -1, dtype=torch.int64)
+            for b, p in enumerate(prompts):
+                forced[b, 1:1 + len(p)] = torch.tensor(p, dtype=torch.int64)
+            stt.forced = forced.repeat_interleave(rep, 0).contiguous().to(self.device)
+
+    def _constrain(self, stt: "DecodeState"):
+        """The step's constraint launch on stt.logits (between the head GEMM and the pick); a beam state's history
+        goes through its ancestor table."""
+        c = stt.cons
+        native.logits_constrain(stt.logits, self.V, stt.ids, stt.pos, group=stt.K or 1, anc=stt.anc if stt.K else None,
+                                finished=stt.finished, repetition_penalty=c.repetition_penalty,
+                                no_repeat_ngram=c.no_repeat_ngram, min_length=c.min_length, end_id=stt.end_id,
+                                suppress=stt.suppress, forced=stt.forced)
+
     def decode_begin(self, mem: torch.Tensor, mem_ld: int, S: int, B: int, max_len: int, start_id: int,
-                     end_id: int) -> "DecodeState":
+                     end_id: int, constraints: Optional[DecodeConstraints] = None) -> "DecodeState":
         """Set up a batched greedy decode over B images whose memory rows are mem [B*S, d] (row
         stride mem_ld): cross-attention K/V of every layer computed once (one fused GEMM), empty
-        self-attention caches, ids[:, 0] = START, position 0 on the device."""
+        self-attention caches, ids[:, 0] = START, position 0 on the device. constraints: DecodeConstraints
+        (inactive or None: the unconstrained step, launch for launch)."""
         if max_len > self.pe.shape[0]:
             raise ValueError(f"max_len {max_len} exceeds the positional table ({self.pe.shape[0]} = "
                              f"decoder_max_seq_len; the reference's PositionalEncoding would fail too)")
         stt = DecodeState(self, B, S, max_len, start_id, end_id)
+        self._constrain_begin(stt, constraints, B, 1)
         d, L, st = self.d, self.L, self.store
         wkv, bkv = st.w("cross_kv.weight"), st.p("cross_kv.bias")
         for l in range(L):
@@ -785,7 +888,11 @@ class TransformerDecoder:
 
     def decode_step(self, stt: "DecodeState"):
         """One greedy token for every row: position p = stt.pos (device) -> ids[:, p+1]; p += 1.
-        No host synchronisation: capturable into a hipGraph."""
+        No host synchronisation: capturable into a hipGraph. With active constraints the head runs as the plain
+        GEMM into f32 logits (as beam_step), the constraint launch edits them, and the pick is the argmax of the
+        edited rows (greedy_pick_advance on the fused state; greedy_pick and step_inc otherwise)."""
+        if stt.cons is not None:
+            return self._decode_step_constrained(stt)
         if stt.fused:
             return self._decode_step_fused(stt)
         x = self._step_body(stt)
@@ -794,6 +901,21 @@ class TransformerDecoder:
         native.greedy_pick(stt.logits, stt.ids, stt.pos, stt.end_id, self.pad_idx, stt.finished, stt.n_finished,
                            V=self.V)
         native.step_inc(stt.pos)
+
+    def _decode_step_constrained(self, stt: "DecodeState"):
+        """decode_step with active constraints: the folded argmax of the fused head gives way to f32 logits in
+        memory, which the constraint launch edits before the pick reads them."""
+        x = self._step_body_fused(stt) if stt.fused else self._step_body(stt)
+        st, w = self.store, self.store.w
+        native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
+        self._constrain(stt)
+        if stt.fused:
+            native.greedy_pick_advance(stt.logits, stt.ids, stt.pos, stt.end_id, self.pad_idx, stt.finished,
+                                       stt.n_finished, stt.ticket, V=self.V)
+        else:
+            native.greedy_pick(stt.logits, stt.ids, stt.pos, stt.end_id, self.pad_idx, stt.finished, stt.n_finished,
+                               V=self.V)
+            native.step_inc(stt.pos)
 
     def _attn_self(self, stt: "DecodeState", cache: torch.Tensor, scale: float):
         """The step's causal self-attention over the cache (query: stt.qkv's first d columns) -> stt.o; a beam
@@ -898,11 +1020,12 @@ class TransformerDecoder:
 
     # --- beam search on the same step (csrc/beam.hip) ---------------------------------------------------
     def beam_begin(self, mem: torch.Tensor, mem_ld: int, S: int, B: int, K: int, max_len: int, start_id: int,
-                   end_id: int) -> "BeamState":
+                   end_id: int, constraints: Optional[DecodeConstraints] = None) -> "BeamState":
         """Set up a beam search of K slots per image over B images (memory rows mem [B*S, d], row stride
         mem_ld): the cross-attention K/V of every layer computed once per IMAGE (its K beams share it), empty
         slot-ordered self-attention caches for the B*K rows, START in every slot, score 0 in slot 0 and -inf in
-        the others, position 0 on the device."""
+        the others, position 0 on the device. constraints: DecodeConstraints; an image's prompt is forced on its K
+        beams, and scores are log_softmax of the constrained rows."""
         if max_len > self.pe.shape[0]:
             raise ValueError(f"max_len {max_len} exceeds the positional table ({self.pe.shape[0]} = "
                              f"decoder_max_seq_len; the reference's PositionalEncoding would fail too)")
@@ -911,6 +1034,7 @@ class TransformerDecoder:
         if max_len < 2:
             raise ValueError("beam search needs max_len >= 2")
         stt = BeamState(self, B, K, S, max_len, start_id, end_id)
+        self._constrain_begin(stt, constraints, B, K)
         d, L, st = self.d, self.L, self.store
         wkv, bkv = st.w("cross_kv.weight"), st.p("cross_kv.bias")
         for l in range(L):
@@ -919,22 +1043,26 @@ class TransformerDecoder:
 
     def beam_step(self, stt: "BeamState"):
         """One token for every beam: the greedy step's body with the ancestry-gathered attention, the head as a
-        plain GEMM into f32 logits [B*K, padded_vocab], then the selection (which advances the position).
+        plain GEMM into f32 logits [B*K, padded_vocab], with active constraints their launch on those rows (each
+        beam's history read through the ancestor table), then the selection (which advances the position).
         No host synchronisation: recordable and capturable like decode_step."""
         x = self._step_body_fused(stt) if stt.fused else self._step_body(stt)
         st, w = self.store, self.store.w
         native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
+        if stt.cons is not None:
+            self._constrain(stt)
         native.beam_select(stt.logits, self.V, stt.score, stt.ids, stt.anc, stt.pos, stt.end_id, self.pad_idx,
                            stt.finished, stt.length, stt.n_finished, stt.ws, stt.images, stt.K)
 
     # --- sampling on the same step (csrc/sample.hip) ------------------------------------------------------
     def sample_begin(self, mem: torch.Tensor, mem_ld: int, S: int, B: int, N: int, max_len: int, start_id: int,
                      end_id: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-                     row0: int = 0) -> "SampleState":
+                     row0: int = 0, constraints: Optional[DecodeConstraints] = None) -> "SampleState":
         """Set up a sampled decode of N samples per image over B images (memory rows mem [B*S, d], row stride
         mem_ld): the cross-attention K/V of every layer computed once per IMAGE, an empty self-attention cache per
         row, START in every row, log-probability 0, position 0 on the device. Row r draws with the uniform of
-        (seed, row0 + r, position)."""
+        (seed, row0 + r, position). constraints: DecodeConstraints; an image's prompt is forced on its N samples,
+        and log-probabilities are log_softmax of the constrained rows."""
         if max_len > self.pe.shape[0]:
             raise ValueError(f"max_len {max_len} exceeds the positional table ({self.pe.shape[0]} = "
                              f"decoder_max_seq_len; the reference's PositionalEncoding would fail too)")
@@ -946,6 +1074,7 @@ class TransformerDecoder:
             raise ValueError(f"sampling needs temperature > 0, top_p > 0 and top_k >= 0 (got {temperature}, {top_p}, "
                              f"{top_k})")
         stt = SampleState(self, B, N, S, max_len, start_id, end_id, temperature, top_k, top_p, seed, row0)
+        self._constrain_begin(stt, constraints, B, N)
         d, L, st = self.d, self.L, self.store
         wkv, bkv = st.w("cross_kv.weight"), st.p("cross_kv.bias")
         for l in range(L):
@@ -955,11 +1084,13 @@ class TransformerDecoder:
     def sample_step(self, stt: "SampleState"):
         """One sampled token for every row: the greedy step's body (each row attends over its own cache, the N
         samples of an image over its one cross-attention K/V), the head as a plain GEMM into f32 logits
-        [B*N, padded_vocab], then the pick (which advances the position). No host synchronisation: recordable
-        and capturable like decode_step."""
+        [B*N, padded_vocab], with active constraints their launch on those rows, then the pick (which advances the
+        position). No host synchronisation: recordable and capturable like decode_step."""
         x = self._step_body_fused(stt) if stt.fused else self._step_body(stt)
         st, w = self.store, self.store.w
         native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
+        if stt.cons is not None:
+            self._constrain(stt)
         native.sample_pick(stt.logits, self.V, stt.temperature, stt.top_k, stt.top_p, stt.seed, stt.row0, None, stt.ids,
                            stt.pos, stt.end_id, self.pad_idx, stt.finished, stt.n_finished, stt.logprob, stt.length,
                            stt.ticket)

@@ -62,7 +62,8 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
                       start_token_id: int = config.START_TOKEN_ID, end_token_id: int = config.END_TOKEN_ID,
                       max_len: int = config.MAX_SEQ_LEN, batch_size: int = 256, beam_size: Optional[int] = None,
                       length_penalty: float = 0.0, temperature: Optional[float] = None, top_k: int = 0,
-                      top_p: float = 1.0, seed: int = 0):
+                      top_p: float = 1.0, seed: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                      min_length: int = 0, suppress_tokens=(), prompts=None):
     """Captions for a list of PIL images / HWC arrays or a [B,3,H,W] pixel tensor, `batch_size` images
     per batched decode. Returns [(processed ids, text)] — text is None without a `decode` function
     (the BPE tokenizer, tokenizer.py, is a host-side library outside this path).
@@ -70,7 +71,21 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
     (generate_beam_batch, ranked by score / length**length_penalty) and post-processes the best beam alike.
     temperature: a number draws each caption from the model's distribution instead (generate_sample_batch with
     top_k / top_p / seed; one sample per image). Image i of `images` draws with (seed, i) whatever the
-    batch_size, so the captions do not depend on how the images are batched."""
+    batch_size, so the captions do not depend on how the images are batched.
+    repetition_penalty / no_repeat_ngram_size / min_length / suppress_tokens / prompts: the decode constraints of
+    generate_batch, generate_beam_batch and generate_sample_batch alike (defaults: off, and then not passed on).
+    prompts is one token list for every image or one list per image of `images`; a prompt's tokens are part of the
+    processed ids and so of the text."""
+    cons = {}
+    if repetition_penalty != 1.0:
+        cons["repetition_penalty"] = repetition_penalty
+    if no_repeat_ngram_size:
+        cons["no_repeat_ngram_size"] = no_repeat_ngram_size
+    if min_length:
+        cons["min_length"] = min_length
+    if suppress_tokens:
+        cons["suppress_tokens"] = tuple(suppress_tokens)
+    per_image = bool(prompts) and all(isinstance(p, (list, tuple)) for p in prompts)
     if temperature is not None and beam_size is not None:
         raise ValueError("generate_captions: choose beam search (beam_size) or sampling (temperature), not both")
     if isinstance(images, torch.Tensor):
@@ -88,15 +103,17 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
     chunk = dev(starts[0]) if starts else None
     for j in range(len(starts)):
         nxt = dev(starts[j + 1]) if j + 1 < len(starts) else None
+        if prompts:  # a list per image is cut with the images
+            cons["prompts"] = list(prompts[starts[j]:starts[j] + batch_size]) if per_image else list(prompts)
         if temperature is not None:
             ids = model.generate_sample_batch(chunk, start_token_id, end_token_id, max_len=max_len,
                                               temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
-                                              image_offset=starts[j])
+                                              image_offset=starts[j], **cons)
         elif beam_size is None:
-            ids = model.generate_batch(chunk, start_token_id, end_token_id, max_len=max_len, next_images=nxt)
+            ids = model.generate_batch(chunk, start_token_id, end_token_id, max_len=max_len, next_images=nxt, **cons)
         else:
             ids = model.generate_beam_batch(chunk, start_token_id, end_token_id, max_len=max_len,
-                                            beam_size=beam_size, length_penalty=length_penalty)
+                                            beam_size=beam_size, length_penalty=length_penalty, **cons)
         chunk = nxt
         for seq in ids:
             p = postprocess_ids(seq, start_token_id, end_token_id)
@@ -138,13 +155,31 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--top_k", type=int, default=0, help="sampling: keep the k most likely tokens (0: all)")
     ap.add_argument("--top_p", type=float, default=1.0, help="sampling: keep the smallest set of this mass (1: all)")
     ap.add_argument("--seed", type=int, default=0, help="sampling seed")
+    ap.add_argument("--repetition_penalty", type=float, default=1.0,
+                    help="divide (positive) / multiply (other) the logit of every token a caption already holds")
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=0, help="no n-gram of this size occurs twice (0: off)")
+    ap.add_argument("--min_length", type=int, default=0, help="no END before this many generated tokens")
+    ap.add_argument("--suppress_tokens", type=int, nargs="*", default=[], help="token ids that are never picked")
+    ap.add_argument("--prompt_ids", type=int, nargs="*", default=[], help="token ids every caption starts with")
     return ap
 
 
 def decode_options(args) -> dict:
-    """The parsed command line as generate_captions keyword arguments."""
-    return dict(batch_size=args.batch_size, beam_size=args.beam_size, length_penalty=args.length_penalty,
-                temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
+    """The parsed command line as generate_captions keyword arguments; a decode constraint is carried where the
+    command line sets it (left at its default it is off, and generate_captions' own default says the same)."""
+    o = dict(batch_size=args.batch_size, beam_size=args.beam_size, length_penalty=args.length_penalty,
+             temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
+    if args.repetition_penalty != 1.0:
+        o["repetition_penalty"] = args.repetition_penalty
+    if args.no_repeat_ngram_size:
+        o["no_repeat_ngram_size"] = args.no_repeat_ngram_size
+    if args.min_length:
+        o["min_length"] = args.min_length
+    if args.suppress_tokens:
+        o["suppress_tokens"] = tuple(args.suppress_tokens)
+    if args.prompt_ids:
+        o["prompts"] = list(args.prompt_ids)
+    return o
 
 
 def main(argv=None):

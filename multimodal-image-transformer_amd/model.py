@@ -27,7 +27,7 @@ import torch
 import config
 import data
 import native
-from decoder import TransformerDecoder, decoder_entries, flat_to_reference, reference_to_flat
+from decoder import DecodeConstraints, TransformerDecoder, decoder_entries, flat_to_reference, reference_to_flat
 from encoder import VisionEncoder, build_encoder
 from params import FlatParams
 
@@ -482,7 +482,9 @@ class ImageToTextModel:
     @torch.no_grad()
     def generate_batch(self, images, start_token_id: int, end_token_id: int, max_len: int = 100,
                        use_graph: bool = True, check_every: int = 8, streams: Optional[int] = None,
-                       next_images: Optional[torch.Tensor] = None) -> List[List[int]]:
+                       next_images: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
+                       no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=(),
+                       prompts=None) -> List[List[int]]:
         """Greedy captions for a whole batch (BASELINE config 5): per image the same token list as
         generate() (model.py:171-242: START, argmax of the last position each step, stop after END,
         at most max_len ids), computed with cached self-attention K/V, the cross-attention K/V of
@@ -498,7 +500,16 @@ class ImageToTextModel:
 
         next_images: the next call's images (pixel values on the device); their frozen encoder forward is
         issued on the encoder stream one launch chunk per token step, beside this call's latency-bound
-        token steps, and the next call takes it (as train_step's next_images; the ids are unchanged)."""
+        token steps, and the next call takes it (as train_step's next_images; the ids are unchanged).
+
+        Constraints (decoder.DecodeConstraints, csrc/constrain.hip; the defaults switch them off and leave the
+        decode launch for launch what it was): repetition_penalty (> 0; the logit of every token a row already
+        holds is divided by it when positive, multiplied otherwise), no_repeat_ngram_size (no n-gram occurs twice
+        in a row's ids), min_length (no END before that many generated tokens), suppress_tokens (ids never picked)
+        and prompts (one token list per image, or one for all images: forced after START and part of the returned
+        ids).
+        With active constraints the head's folded argmax gives way to f32 logits, the constraint launch and the
+        pick; a prompt list per image is split with the rows when streams > 1."""
         self.eval()
         pv = images if isinstance(images, torch.Tensor) else \
             self.image_processor(images=images, return_tensors="pt")["pixel_values"]
@@ -510,8 +521,13 @@ class ImageToTextModel:
             streams = int(os.environ.get("MIT_DECODE_STREAMS", "1"))
         G = max(1, min(int(streams), B))
         bounds = [B * i // G for i in range(G + 1)]
+        cons = DecodeConstraints(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts)
+        if cons.active():  # the whole batch's prompt lists, before they are cut into row groups
+            cons.validate(dec.V, max_len, int(end_token_id), B)
         states = [dec.decode_begin(mem[bounds[i] * S:bounds[i + 1] * S], mem_ld, S, bounds[i + 1] - bounds[i], max_len,
-                                   start_token_id, end_token_id) for i in range(G)]
+                                   start_token_id, end_token_id,
+                                   constraints=cons.rows(bounds[i], bounds[i + 1]) if cons.active() else None)
+                  for i in range(G)]
         steps = max_len - 1
         if steps > 0:
             for stt in states:
@@ -572,7 +588,8 @@ class ImageToTextModel:
     @torch.no_grad()
     def generate_beam_batch(self, images, start_token_id: int, end_token_id: int, max_len: int = 100,
                             beam_size: int = config.BEAM_SIZE, length_penalty: float = 0.0, return_all: bool = False,
-                            use_graph: bool = True, check_every: int = 8):
+                            use_graph: bool = True, check_every: int = 8, repetition_penalty: float = 1.0,
+                            no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=(), prompts=None):
         """Beam-search captions for a whole batch: beam_size slots per image on the KV-cache step of
         generate_batch (decoder.beam_begin / beam_step). Per step a live beam offers its V continuations at
         score + log_softmax(logits), a finished beam itself once (padded); the beam_size best by (score, lower
@@ -584,7 +601,12 @@ class ImageToTextModel:
         Beams are ranked on the host by score / length**length_penalty (length: generated tokens, END included;
         0.0 ranks by the raw log-probability), ties to the lower slot. Returns per image the best beam's ids
         (START .. first END inclusive, else max_len ids), or with return_all its beam_size (ids, score) pairs,
-        best first."""
+        best first.
+
+        repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts: the constraints of
+        generate_batch (the defaults switch them off and leave the decode launch for launch what it was).
+        A beam's constraints follow its own ids (its ancestry), scores are log_softmax of the constrained logits,
+        and a prompt adds nothing to a score."""
         self.eval()
         pv = images if isinstance(images, torch.Tensor) else \
             self.image_processor(images=images, return_tensors="pt")["pixel_values"]
@@ -592,7 +614,9 @@ class ImageToTextModel:
         B, K = pv.shape[0], int(beam_size)
         mem, mem_ld, S, _, _ = self._encode_memory(pv)
         dec = self.decoder
-        stt = dec.beam_begin(mem, mem_ld, S, B, K, max_len, start_token_id, end_token_id)
+        cons = DecodeConstraints(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts)
+        stt = dec.beam_begin(mem, mem_ld, S, B, K, max_len, start_token_id, end_token_id,
+                             constraints=cons if cons.active() else None)
         steps = max_len - 1
         dec.beam_step(stt)  # position 0 (eager: warms every kernel before capture)
         done = 1
@@ -620,20 +644,23 @@ class ImageToTextModel:
 
     @torch.no_grad()
     def generate_beam(self, image, start_token_id: int, end_token_id: int, max_len: int = 100,
-                      beam_size: int = config.BEAM_SIZE, length_penalty: float = 0.0, return_all: bool = False):
-        """generate_beam_batch for one image (a PIL image / HWC array or a [3,H,W] / [1,3,H,W] pixel tensor)."""
+                      beam_size: int = config.BEAM_SIZE, length_penalty: float = 0.0, return_all: bool = False,
+                      **constraints):
+        """generate_beam_batch for one image (a PIL image / HWC array or a [3,H,W] / [1,3,H,W] pixel tensor);
+        further keyword arguments: generate_beam_batch's constraints."""
         if isinstance(image, torch.Tensor):
             pv = image if image.dim() == 4 else image.unsqueeze(0)
         else:
             pv = self.image_processor(images=image, return_tensors="pt")["pixel_values"]
         return self.generate_beam_batch(pv, start_token_id, end_token_id, max_len=max_len, beam_size=beam_size,
-                                        length_penalty=length_penalty, return_all=return_all)[0]
+                                        length_penalty=length_penalty, return_all=return_all, **constraints)[0]
 
     @torch.no_grad()
     def generate_sample_batch(self, images, start_token_id: int, end_token_id: int, max_len: int = 100,
                               temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_samples: int = 1,
                               seed: int = 0, image_offset: int = 0, return_logprob: bool = False,
-                              use_graph: bool = True, check_every: int = 8):
+                              use_graph: bool = True, check_every: int = 8, repetition_penalty: float = 1.0,
+                              no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=(), prompts=None):
         """Sampled captions for a whole batch: num_samples rows per image on the KV-cache step of generate_batch
         (decoder.sample_begin / sample_step). Per step a live row draws its next token from softmax(logits /
         temperature) restricted to the top_k most likely tokens and, inside them, to the shortest prefix of mass
@@ -646,7 +673,11 @@ class ImageToTextModel:
 
         Returns per image its ids (START .. first END inclusive, else max_len ids) when num_samples == 1 and
         return_logprob is False; else per image its num_samples (ids, logprob) pairs, logprob being the sum of
-        log_softmax(logits)[token] (temperature 1, unfiltered) over the generated tokens, END included."""
+        log_softmax(logits)[token] (temperature 1, unfiltered) over the generated tokens, END included.
+
+        repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts: the constraints of
+        generate_batch (the defaults switch them off and leave the decode launch for launch what it was).
+        The draw and the logprob are taken from the constrained logits; a prompt adds nothing to a logprob."""
         self.eval()
         pv = images if isinstance(images, torch.Tensor) else \
             self.image_processor(images=images, return_tensors="pt")["pixel_values"]
@@ -654,8 +685,10 @@ class ImageToTextModel:
         B, N = pv.shape[0], int(num_samples)
         mem, mem_ld, S, _, _ = self._encode_memory(pv)
         dec = self.decoder
+        cons = DecodeConstraints(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts)
         stt = dec.sample_begin(mem, mem_ld, S, B, N, max_len, start_token_id, end_token_id, temperature=temperature,
-                               top_k=top_k, top_p=top_p, seed=seed, row0=int(image_offset) * N)
+                               top_k=top_k, top_p=top_p, seed=seed, row0=int(image_offset) * N,
+                               constraints=cons if cons.active() else None)
         steps = max_len - 1
         dec.sample_step(stt)  # position 0 (eager: warms every kernel before capture)
         done = 1

@@ -183,6 +183,7 @@ SIGNATURES = {
     "mit_sample_uniform": (I, [L, L, vp, vp, vp, vp]),
     "mit_sample_pick": (I, [L, L, vp, L, Fl, L, Fl, vp, L, vp, vp, L, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp,
                             vp, vp, vp]),
+    "mit_logits_constrain": (I, [L, L, vp, L, vp, L, vp, L, vp, L, vp, Fl, L, L, ctypes.c_int64, vp, L, vp, L, vp]),
 }
 
 
@@ -969,6 +970,21 @@ def sample_pick(logits, V, temperature, top_k, top_p, seed, row0, uniforms, ids,
                                  float(top_p), ptr(seed), int(row0), ptr(uniforms), ptr(ids), ids.stride(0), ptr(pos),
                                  int(end_id), int(pad_id), ptr(finished), ptr(n_finished), ptr(logprob), ptr(length),
                                  ptr(ticket), stream_ptr()), "mit_sample_pick")
+
+
+# --- constrained decoding (constrain.hip) -------------------------------------------------------------
+def logits_constrain(logits, V, tok, pos, *, group=1, anc=None, finished=None, repetition_penalty=1.0,
+                     no_repeat_ngram=0, min_length=0, end_id=-1, suppress=None, forced=None):
+    """Edit the f32 logits rows [R, ld] of a token step in place before its pick (mit_logits_constrain): repetition
+    penalty, no-repeat n-gram, minimum length, suppressed tokens (int64 device array) and forced tokens (int64
+    [R, ld_forced], -1 = free), over each row's history tok[:, 0 .. pos] (read through the ancestor table anc for a
+    beam state, group = its beam size). The picks treat the edited row as the model's logits."""
+    _check(lib().mit_logits_constrain(logits.shape[0], V, ptr(logits), logits.stride(0), ptr(tok), tok.stride(0),
+                                      ptr(pos), int(group), ptr(anc), anc.stride(0) if anc is not None else 0,
+                                      ptr(finished), float(repetition_penalty), int(no_repeat_ngram), int(min_length),
+                                      int(end_id), ptr(suppress), suppress.numel() if suppress is not None else 0,
+                                      ptr(forced), forced.stride(0) if forced is not None else 0, stream_ptr()),
+           "mit_logits_constrain")
 
 
 def image_normalize(src_u8, dst, mean, std):
