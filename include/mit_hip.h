@@ -674,6 +674,51 @@ int mit_logits_constrain(long R, long V, float* logits, long ld, const int64_t* 
                          long n_suppress, const int64_t* forced, long ld_forced, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * FP8 cross-attention K / V for the decode step (csrc/kv8.hip; additive since ABI 9, opt-in: the bf16 entry points
+ * above are what a decode uses unless asked). The image memory's K | V rows, which every token step streams once,
+ * stored as OCP e4m3fn bytes (never fnuz) with one power-of-two f32 scale per (image, head) for K and one for V.
+ * e4m3 has 4 significant bits, so byte * 2^e is exact in bf16: the quantised attention is mit_attention_decode's
+ * on the dequantised values, up to the f32 arithmetic both share. Only the cross-attention K / V is quantised.
+ *
+ * kv_quantize_fp8: B images of S rows; a row holds G groups of Dh consecutive columns (a K | V row of width 2d:
+ *   G = 2H, the K heads then the V heads). Per image b and group g, over the S x Dh bf16 values x widened to f32:
+ *     amax = max |x| = m * 2^X, m in [1, 2);  e = X - 8 if m <= 1.75, else X - 7 (the smallest e with
+ *     amax * 2^-e <= 448), clamped to [-64, 64]; e = 0 if amax == 0. Integer arithmetic on the float's bits.
+ *     scales[b*G + g] = 2^e;  dst[b*d_batch + j*d_row + g*Dh + i] = e4m3fn_rne(x * 2^-e)   (the product is exact,
+ *     at most 448: saturation never acts; -0 keeps its sign)
+ *   src bf16, strides s_row / s_batch in elements; dst bytes, strides d_row / d_batch in bytes; scales f32 [B][G]
+ *   dense. Written: exactly the G*Dh bytes of each of the S rows of each image, and B*G scales; nothing between the
+ *   rows or the batches is read or written. Non-finite inputs and amax beyond 448 * 2^64 give unspecified values
+ *   (nothing out of bounds is touched). Dh in {16, 32, 64, 128}; src, dst and every stride in bytes 16-B aligned;
+ *   scales 4-B aligned; G >= 1; B * G < 2^31. Deterministic (a maximum is order-free; no float atomics): a second
+ *   launch is bitwise equal. B == 0 or S == 0 launches nothing. Asynchronous, recordable.
+ * attention_decode_fp8: the cross-attention of mit_attention_decode (fixed Lk > 0; no position, no key-padding
+ *   mask, no ancestor table) over R rows of bf16 queries; row r reads the K / V bytes and the scales of image
+ *   r / group (R % group == 0: the beams or samples of an image share its one K / V):
+ *     o[r, h*Dh + i] = sum_j softmax_j(scale * ks * q_rh . k8_j) * vs * v8_ji,
+ *     ks = k_scale[(r/group)*scale_batch + h], vs = v_scale[(r/group)*scale_batch + h]
+ *   The K scale folds into the pre-scaled query and the V scale into the final 1/l, both exactly. q, o bf16 with
+ *   strides in elements; k, v e4m3 bytes with strides in bytes; rows j >= Lk and bytes past column H*Dh of a row are
+ *   never read. q, k, v, o and every stride in bytes 16-B aligned; scales 4-B aligned; Dh in {16, 32, 64, 128};
+ *   group >= 1; R >= 0, H >= 1, R * H < 2^31; scale_batch >= H. R = 0 launches nothing. Two families (MIT_DECODE_ATTN_FP8_*): for H*Dh == 512 one
+ *   block per ROW streams the image's contiguous 512-B rows non-temporally (the structure of
+ *   MIT_DECODE_ATTN_ROWS_NT; the `group` rows of an image are `group` blocks on the same bytes, so group > 1 is
+ *   bitwise group = 1 on repeated K / V); otherwise one block per (row, head) (the structure of
+ *   MIT_DECODE_ATTN_BH). Deterministic; asynchronous, recordable.
+ * mit_attention_decode_fp8_plan: the family the call would launch, from the same host decision function; -1 for
+ *   arguments it rejects. No launch, no pointer is dereferenced, no GPU needed. */
+enum { MIT_DECODE_ATTN_FP8_BH = 3, MIT_DECODE_ATTN_FP8_ROWS = 4 };
+int mit_kv_quantize_fp8(long B, long S, long G, long Dh, const void* src, long s_row, long s_batch, void* dst, long d_row,
+                        long d_batch, float* scales, void* stream);
+int mit_attention_decode_fp8_plan(long R, long H, long Dh, const void* q, long q_batch, const void* k, long k_row,
+                                  long k_batch, const void* v, long v_row, long v_batch, const float* k_scale,
+                                  const float* v_scale, long scale_batch, const void* o, long o_batch, long Lk,
+                                  long group);
+int mit_attention_decode_fp8(long R, long H, long Dh, const void* q, long q_batch, const void* k, long k_row, long k_batch,
+                             const void* v, long v_row, long v_batch, const float* k_scale, const float* v_scale,
+                             long scale_batch, void* o, long o_batch, long Lk, long group, float scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Utilities. cast: f32 -> operand dtype copy (weights to the bf16 shadow); fill f32.
  * dropout_mask_debug: writes the keep-multiplier (0 or 1/(1-p)) the kernels use at
  * (seed, site, idx) for idx in [0, n) — tests rebuild reference masks from it.

@@ -101,22 +101,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(long H, const T* __res
 // 8l / DH, and a head's score is reduced over its DH / 8 lanes -- so a block streams its image's K/V
 // rows contiguously (the (b, h)-block kernel reads 128-B pieces of every row, 8 times per DRAM page)
 // with U rows per wave in flight before the first use. Wave w takes keys w*U .. w*U+U-1 (+8U per
-// iteration); the 8 waves' softmax states merge once in LDS.
-// sum over the LPH (2 / 4 / 8 / 16) consecutive lanes of a head by DPP: quad_perm [1,0,3,2] and
-// [2,3,0,1], then row_half_mirror (lane i <-> 7 - i: the other quad's sum) and row_mirror (i <-> 15 - i)
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, false));
-}
-template <int LPH>
-__device__ __forceinline__ float head_sum(float v) {
-  if constexpr (LPH >= 2) v += dpp_f<0xB1>(v);
-  if constexpr (LPH >= 4) v += dpp_f<0x4E>(v);
-  if constexpr (LPH >= 8) v += dpp_f<0x141>(v);
-  if constexpr (LPH >= 16) v += dpp_f<0x140>(v);
-  return v;
-}
-
+// iteration); the 8 waves' softmax states merge once in LDS. A head's score is summed over its lanes by
+// head_sum (decode_attn.h).
 template <int DH, int U, bool NT>
 __global__ __launch_bounds__(512) void attn_decode_rows_kernel(const bf16* __restrict__ q, long q_batch,
                                                                const bf16* __restrict__ k, long k_row, long k_batch,

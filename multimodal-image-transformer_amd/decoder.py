@@ -325,12 +325,33 @@ class DecodeConstraints:
                     raise ValueError(f"prompt: contains END ({end_id})")
 
 
+KV_DTYPES = ("bf16", "fp8")
+
+
+def resolve_kv_dtype(kv_dtype: Optional[str] = None, dtype: torch.dtype = torch.bfloat16) -> str:
+    """The storage of a decode's cross-attention K/V: the argument, else env MIT_DECODE_KV, else "bf16" (which
+    means the decoder's own dtype: the state as it always was). "fp8": OCP e4m3fn bytes with a power-of-two scale
+    per (layer, image, head) for K and one for V (csrc/kv8.hip), half the bytes every token step streams and half
+    the memory a batch's K/V holds; bf16 decoders only."""
+    v = kv_dtype if kv_dtype is not None else os.environ.get("MIT_DECODE_KV") or "bf16"
+    if v not in KV_DTYPES:
+        raise ValueError(f"kv_dtype {v!r}: choose one of {KV_DTYPES}")
+    if v == "fp8" and dtype != torch.bfloat16:
+        raise ValueError(f"kv_dtype 'fp8' needs a bfloat16 decoder (this one is {dtype}): the quantiser reads bf16 "
+                         f"K/V rows and the FP8 attention kernels take bf16 queries; float32 is the parity mode")
+    return v
+
+
 class DecodeState:
     """Device state of a batched greedy decode (TransformerDecoder.decode_begin / decode_step):
     token ids [B, max_len] (int64; column 0 = START), the device position, per-row finished flags
-    and their count, the cross-attention K/V of all layers [B*S, L*2d], per-layer self-attention
+    and their count, the cross-attention K/V of all layers [L, B*S, 2d] (or, with kv_dtype "fp8", its e4m3 bytes
+    kv8 and the scales kv_scale [L, images, 2H]: K heads, then V heads), per-layer self-attention
     caches [B, max_len, 2d] (K | V), and the B-row activations of one token step."""
 
+    kv: Optional[torch.Tensor] = None        # [L, images*S, 2d] in the decoder's dtype; None with kv_dtype "fp8"
+    kv8: Optional[torch.Tensor] = None       # fp8: uint8 [L, images*S, 2d] (K | V as kv)
+    kv_scale: Optional[torch.Tensor] = None  # fp8: f32 [L, images, 2H]
     K = 0  # beam slots per image (BeamState); 0: greedy rows
     group = 1  # rows that share one cross-attention memory (SampleState: the samples of an image)
     cons: Optional[DecodeConstraints] = None  # active constraints (TransformerDecoder._constrain_begin), else None
@@ -338,10 +359,12 @@ class DecodeState:
     forced: Optional[torch.Tensor] = None     # with cons: int64 [rows, Lp + 1], column j + 1 = prompt token j, -1 = free
 
     def __init__(self, dec: "TransformerDecoder", B: int, S: int, max_len: int, start_id: int, end_id: int,
-                 images: Optional[int] = None):
-        """B rows; images: how many memories the cross-attention K/V holds (default: one per row)."""
+                 images: Optional[int] = None, kv_dtype: Optional[str] = None):
+        """B rows; images: how many memories the cross-attention K/V holds (default: one per row); kv_dtype:
+        resolve_kv_dtype."""
         dev, dt = dec.device, dec.dtype
         d, F, L, V = dec.d, dec.F, dec.L, dec.V
+        self.kv_dtype = resolve_kv_dtype(kv_dtype, dt)
         self.B, self.S, self.max_len, self.end_id = B, S, max_len, int(end_id)
         self.ids = torch.full((B, max_len), dec.pad_idx, dtype=torch.int64, device=dev)
         self.ids[:, 0] = int(start_id)
@@ -351,7 +374,12 @@ class DecodeState:
         # per layer contiguous [L][B*S][2d] (K | V): a decode attention block (b, h) then reads its S keys
         # at a 2 KiB stride instead of the training layout's L * 2d row (12 KiB at cfg1), which left the
         # S = 197 cross attention at ~2.6 TB/s on DRAM page misses
-        self.kv = torch.empty(L, (B if images is None else images) * S, 2 * d, dtype=dt, device=dev)
+        n_img = B if images is None else images
+        if self.kv_dtype == "fp8":  # no bf16 K/V is held: each layer's rows pass through one staging buffer
+            self.kv8 = torch.empty(L, n_img * S, 2 * d, dtype=torch.uint8, device=dev)
+            self.kv_scale = torch.empty(L, n_img, 2 * dec.H, dtype=torch.float32, device=dev)
+        else:
+            self.kv = torch.empty(L, n_img * S, 2 * d, dtype=dt, device=dev)
         self.cache = [torch.empty(B, max_len, 2 * d, dtype=dt, device=dev) for _ in range(L)]
         e = lambda n: torch.empty(B, n, dtype=dt, device=dev)  # noqa: E731
         self.x, self.x1, self.x2, self.y, self.o, self.q = e(d), e(d), e(d), e(d), e(d), e(d)
@@ -386,8 +414,8 @@ class BeamState(DecodeState):
     row holds position j of the beam now in slot r. The cross-attention K/V holds one memory per image."""
 
     def __init__(self, dec: "TransformerDecoder", images: int, K: int, S: int, max_len: int, start_id: int,
-                 end_id: int):
-        super().__init__(dec, images * K, S, max_len, start_id, end_id, images=images)
+                 end_id: int, kv_dtype: Optional[str] = None):
+        super().__init__(dec, images * K, S, max_len, start_id, end_id, images=images, kv_dtype=kv_dtype)
         dev = dec.device
         self.images, self.K = images, K
         self.score = torch.full((images, K), float("-inf"), dtype=torch.float32, device=dev)
@@ -421,8 +449,9 @@ class SampleState(DecodeState):
     settings. The cross-attention K/V holds one memory per image, read by its N samples (group = N)."""
 
     def __init__(self, dec: "TransformerDecoder", images: int, N: int, S: int, max_len: int, start_id: int,
-                 end_id: int, temperature: float, top_k: int, top_p: float, seed: int, row0: int):
-        super().__init__(dec, images * N, S, max_len, start_id, end_id, images=images)
+                 end_id: int, temperature: float, top_k: int, top_p: float, seed: int, row0: int,
+                 kv_dtype: Optional[str] = None):
+        super().__init__(dec, images * N, S, max_len, start_id, end_id, images=images, kv_dtype=kv_dtype)
         dev = dec.device
         self.images, self.group = images, N
         self.temperature, self.top_k, self.top_p, self.row0 = float(temperature), int(top_k), float(top_p), int(row0)
@@ -869,21 +898,35 @@ class TransformerDecoder:
                                 no_repeat_ngram=c.no_repeat_ngram, min_length=c.min_length, end_id=stt.end_id,
                                 suppress=stt.suppress, forced=stt.forced)
 
+    def _cross_kv_begin(self, stt: "DecodeState", mem: torch.Tensor, mem_ld: int, S: int, B: int):
+        """The cross-attention K | V of every layer for the B images of mem, once per decode (one GEMM per layer).
+        An fp8 state gets each layer through one bf16 staging buffer [B*S, 2d], quantised from there (2H groups of
+        head_dim columns per row: the K heads, then the V heads) and released when this returns."""
+        d, L, st = self.d, self.L, self.store
+        wkv, bkv = st.w("cross_kv.weight"), st.p("cross_kv.bias")
+        fp8 = stt.kv8 is not None
+        stage = torch.empty(B * S, 2 * d, dtype=self.dtype, device=self.device) if fp8 else None
+        for l in range(L):
+            native.gemm(mem, wkv[l * 2 * d:], stage if fp8 else stt.kv[l], B * S, 2 * d, d, lda=mem_ld,
+                        bias=bkv[l * 2 * d:])
+            if fp8:
+                native.kv_quantize_fp8(stage, 2 * d, S * 2 * d, stt.kv8[l], 2 * d, S * 2 * d, stt.kv_scale[l], B, S,
+                                       2 * self.H, Dh=self.hd)
+
     def decode_begin(self, mem: torch.Tensor, mem_ld: int, S: int, B: int, max_len: int, start_id: int,
-                     end_id: int, constraints: Optional[DecodeConstraints] = None) -> "DecodeState":
+                     end_id: int, constraints: Optional[DecodeConstraints] = None,
+                     kv_dtype: Optional[str] = None) -> "DecodeState":
         """Set up a batched greedy decode over B images whose memory rows are mem [B*S, d] (row
         stride mem_ld): cross-attention K/V of every layer computed once (one fused GEMM), empty
         self-attention caches, ids[:, 0] = START, position 0 on the device. constraints: DecodeConstraints
-        (inactive or None: the unconstrained step, launch for launch)."""
+        (inactive or None: the unconstrained step, launch for launch). kv_dtype: resolve_kv_dtype ("fp8": the
+        cross-attention K/V as e4m3 bytes, quantised here once; unset, the state and every launch as before)."""
         if max_len > self.pe.shape[0]:
             raise ValueError(f"max_len {max_len} exceeds the positional table ({self.pe.shape[0]} = "
                              f"decoder_max_seq_len; the reference's PositionalEncoding would fail too)")
-        stt = DecodeState(self, B, S, max_len, start_id, end_id)
+        stt = DecodeState(self, B, S, max_len, start_id, end_id, kv_dtype=kv_dtype)
         self._constrain_begin(stt, constraints, B, 1)
-        d, L, st = self.d, self.L, self.store
-        wkv, bkv = st.w("cross_kv.weight"), st.p("cross_kv.bias")
-        for l in range(L):
-            native.gemm(mem, wkv[l * 2 * d:], stt.kv[l], B * S, 2 * d, d, lda=mem_ld, bias=bkv[l * 2 * d:])
+        self._cross_kv_begin(stt, mem, mem_ld, S, B)
         return stt
 
     def decode_step(self, stt: "DecodeState"):
@@ -931,10 +974,16 @@ class TransformerDecoder:
                                     d, stt.B, self.H, pos=stt.pos, key_tokens=stt.ids, tok_batch=Tm,
                                     pad_idx=self.pad_idx, scale=scale, Dh=self.hd)
 
-    def _attn_cross(self, stt: "DecodeState", kvl: torch.Tensor, scale: float):
-        """The step's cross-attention of stt.q over the image memory's K | V rows kvl -> stt.o; the K beams of an
-        image share its one K/V."""
+    def _attn_cross(self, stt: "DecodeState", l: int, scale: float):
+        """The step's cross-attention of stt.q over the image memory's K | V rows of layer l -> stt.o; the K beams
+        (or the samples) of an image share its one K/V. An fp8 state goes to the FP8 kernels (csrc/kv8.hip)."""
         d, S = self.d, stt.S
+        if stt.kv8 is not None:
+            k8, sc, H = stt.kv8[l], stt.kv_scale[l], self.H
+            native.attention_decode_fp8(stt.q, d, k8, 2 * d, S * 2 * d, k8[:, d:], 2 * d, S * 2 * d, sc, sc[:, H:], 2 * H,
+                                        stt.o, d, stt.B, H, Lk=S, group=stt.K or stt.group, scale=scale, Dh=self.hd)
+            return
+        kvl = stt.kv[l]
         if stt.K or stt.group > 1:  # the slots (beam) or samples of an image read its one K/V
             native.attention_decode_beam(stt.q, d, kvl, 2 * d, S * 2 * d, kvl[:, d:], 2 * d, S * 2 * d, stt.o, d, stt.B,
                                          self.H, Lk=S, group=stt.K or stt.group, scale=scale, Dh=self.hd)
@@ -958,7 +1007,7 @@ class TransformerDecoder:
             native.linear(stt.o, w(pre + "self_out.weight"), stt.y, bias=st.p(pre + "self_out.bias"))
             native.layernorm_fwd(x, st.p(pre + "norm1.weight"), st.p(pre + "norm1.bias"), 1e-5, stt.x1, r=stt.y)
             native.linear(stt.x1, w(pre + "cross_q.weight"), stt.q, bias=st.p(pre + "cross_q.bias"))
-            self._attn_cross(stt, stt.kv[l], 1.0 / math.sqrt(self.hd))
+            self._attn_cross(stt, l, 1.0 / math.sqrt(self.hd))
             native.linear(stt.o, w(pre + "cross_out.weight"), stt.y, bias=st.p(pre + "cross_out.bias"))
             native.layernorm_fwd(stt.x1, st.p(pre + "norm2.weight"), st.p(pre + "norm2.bias"), 1e-5, stt.x2, r=stt.y)
             native.linear(stt.x2, w(pre + "linear1.weight"), stt.h, bias=st.p(pre + "linear1.bias"),
@@ -1007,7 +1056,7 @@ class TransformerDecoder:
             native.decode_gemm(stt.o, w(pre + "self_out.weight"), bias=p(pre + "self_out.bias"), residual=a, r_ln=a_ln,
                                z_out=z1, stats_out=s1)
             native.decode_gemm(z1, w(pre + "cross_q.weight"), out=stt.q, bias=p(pre + "cross_q.bias"), a_ln=ln1)
-            self._attn_cross(stt, stt.kv[l], scale)
+            self._attn_cross(stt, l, scale)
             native.decode_gemm(stt.o, w(pre + "cross_out.weight"), bias=p(pre + "cross_out.bias"), residual=z1,
                                r_ln=ln1, z_out=z2, stats_out=s2)
             native.decode_gemm(z2, w(pre + "linear1.weight"), out=stt.h, bias=p(pre + "linear1.bias"),
@@ -1020,7 +1069,8 @@ class TransformerDecoder:
 
     # --- beam search on the same step (csrc/beam.hip) ---------------------------------------------------
     def beam_begin(self, mem: torch.Tensor, mem_ld: int, S: int, B: int, K: int, max_len: int, start_id: int,
-                   end_id: int, constraints: Optional[DecodeConstraints] = None) -> "BeamState":
+                   end_id: int, constraints: Optional[DecodeConstraints] = None,
+                   kv_dtype: Optional[str] = None) -> "BeamState":
         """Set up a beam search of K slots per image over B images (memory rows mem [B*S, d], row stride
         mem_ld): the cross-attention K/V of every layer computed once per IMAGE (its K beams share it), empty
         slot-ordered self-attention caches for the B*K rows, START in every slot, score 0 in slot 0 and -inf in
@@ -1033,12 +1083,9 @@ class TransformerDecoder:
             raise ValueError(f"beam_size {K} must be in 1..8 and at most the vocabulary ({self.V})")
         if max_len < 2:
             raise ValueError("beam search needs max_len >= 2")
-        stt = BeamState(self, B, K, S, max_len, start_id, end_id)
+        stt = BeamState(self, B, K, S, max_len, start_id, end_id, kv_dtype=kv_dtype)
         self._constrain_begin(stt, constraints, B, K)
-        d, L, st = self.d, self.L, self.store
-        wkv, bkv = st.w("cross_kv.weight"), st.p("cross_kv.bias")
-        for l in range(L):
-            native.gemm(mem, wkv[l * 2 * d:], stt.kv[l], B * S, 2 * d, d, lda=mem_ld, bias=bkv[l * 2 * d:])
+        self._cross_kv_begin(stt, mem, mem_ld, S, B)
         return stt
 
     def beam_step(self, stt: "BeamState"):
@@ -1057,7 +1104,8 @@ class TransformerDecoder:
     # --- sampling on the same step (csrc/sample.hip) ------------------------------------------------------
     def sample_begin(self, mem: torch.Tensor, mem_ld: int, S: int, B: int, N: int, max_len: int, start_id: int,
                      end_id: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-                     row0: int = 0, constraints: Optional[DecodeConstraints] = None) -> "SampleState":
+                     row0: int = 0, constraints: Optional[DecodeConstraints] = None,
+                     kv_dtype: Optional[str] = None) -> "SampleState":
         """Set up a sampled decode of N samples per image over B images (memory rows mem [B*S, d], row stride
         mem_ld): the cross-attention K/V of every layer computed once per IMAGE, an empty self-attention cache per
         row, START in every row, log-probability 0, position 0 on the device. Row r draws with the uniform of
@@ -1073,12 +1121,10 @@ class TransformerDecoder:
         if not temperature > 0 or not top_p > 0 or top_k < 0:
             raise ValueError(f"sampling needs temperature > 0, top_p > 0 and top_k >= 0 (got {temperature}, {top_p}, "
                              f"{top_k})")
-        stt = SampleState(self, B, N, S, max_len, start_id, end_id, temperature, top_k, top_p, seed, row0)
+        stt = SampleState(self, B, N, S, max_len, start_id, end_id, temperature, top_k, top_p, seed, row0,
+                          kv_dtype=kv_dtype)
         self._constrain_begin(stt, constraints, B, N)
-        d, L, st = self.d, self.L, self.store
-        wkv, bkv = st.w("cross_kv.weight"), st.p("cross_kv.bias")
-        for l in range(L):
-            native.gemm(mem, wkv[l * 2 * d:], stt.kv[l], B * S, 2 * d, d, lda=mem_ld, bias=bkv[l * 2 * d:])
+        self._cross_kv_begin(stt, mem, mem_ld, S, B)
         return stt
 
     def sample_step(self, stt: "SampleState"):

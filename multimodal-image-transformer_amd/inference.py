@@ -63,7 +63,7 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
                       max_len: int = config.MAX_SEQ_LEN, batch_size: int = 256, beam_size: Optional[int] = None,
                       length_penalty: float = 0.0, temperature: Optional[float] = None, top_k: int = 0,
                       top_p: float = 1.0, seed: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
-                      min_length: int = 0, suppress_tokens=(), prompts=None):
+                      min_length: int = 0, suppress_tokens=(), prompts=None, kv_dtype: Optional[str] = None):
     """Captions for a list of PIL images / HWC arrays or a [B,3,H,W] pixel tensor, `batch_size` images
     per batched decode. Returns [(processed ids, text)] — text is None without a `decode` function
     (the BPE tokenizer, tokenizer.py, is a host-side library outside this path).
@@ -75,8 +75,12 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
     repetition_penalty / no_repeat_ngram_size / min_length / suppress_tokens / prompts: the decode constraints of
     generate_batch, generate_beam_batch and generate_sample_batch alike (defaults: off, and then not passed on).
     prompts is one token list for every image or one list per image of `images`; a prompt's tokens are part of the
-    processed ids and so of the text."""
+    processed ids and so of the text.
+    kv_dtype: "bf16" or "fp8", how the decode holds the cross-attention K/V (generate_batch); passed on only when
+    given, as the constraints are."""
     cons = {}
+    if kv_dtype is not None:
+        cons["kv_dtype"] = kv_dtype
     if repetition_penalty != 1.0:
         cons["repetition_penalty"] = repetition_penalty
     if no_repeat_ngram_size:
@@ -161,6 +165,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--min_length", type=int, default=0, help="no END before this many generated tokens")
     ap.add_argument("--suppress_tokens", type=int, nargs="*", default=[], help="token ids that are never picked")
     ap.add_argument("--prompt_ids", type=int, nargs="*", default=[], help="token ids every caption starts with")
+    ap.add_argument("--kv_dtype", choices=["bf16", "fp8"], default=None,
+                    help="storage of the cross-attention K/V: fp8 halves its memory and the bytes a token step streams "
+                         "(bf16 checkpoints; default: env MIT_DECODE_KV, else bf16)")
     return ap
 
 
@@ -179,6 +186,8 @@ def decode_options(args) -> dict:
         o["suppress_tokens"] = tuple(args.suppress_tokens)
     if args.prompt_ids:
         o["prompts"] = list(args.prompt_ids)
+    if args.kv_dtype is not None:
+        o["kv_dtype"] = args.kv_dtype
     return o
 
 

@@ -484,7 +484,7 @@ class ImageToTextModel:
                        use_graph: bool = True, check_every: int = 8, streams: Optional[int] = None,
                        next_images: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0,
                        no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=(),
-                       prompts=None) -> List[List[int]]:
+                       prompts=None, kv_dtype: Optional[str] = None) -> List[List[int]]:
         """Greedy captions for a whole batch (BASELINE config 5): per image the same token list as
         generate() (model.py:171-242: START, argmax of the last position each step, stop after END,
         at most max_len ids), computed with cached self-attention K/V, the cross-attention K/V of
@@ -509,7 +509,12 @@ class ImageToTextModel:
         and prompts (one token list per image, or one for all images: forced after START and part of the returned
         ids).
         With active constraints the head's folded argmax gives way to f32 logits, the constraint launch and the
-        pick; a prompt list per image is split with the rows when streams > 1."""
+        pick; a prompt list per image is split with the rows when streams > 1.
+
+        kv_dtype: how the cross-attention K/V is held (decoder.resolve_kv_dtype: the argument, else env
+        MIT_DECODE_KV, else "bf16", the decode as it always was). "fp8" (bf16 models) keeps it as e4m3 bytes with
+        power-of-two scales per (layer, image, head): half the bytes a token step streams and half the memory a
+        batch's K/V occupies; the ids are those of the bf16 decode on the dequantised K/V."""
         self.eval()
         pv = images if isinstance(images, torch.Tensor) else \
             self.image_processor(images=images, return_tensors="pt")["pixel_values"]
@@ -526,7 +531,8 @@ class ImageToTextModel:
             cons.validate(dec.V, max_len, int(end_token_id), B)
         states = [dec.decode_begin(mem[bounds[i] * S:bounds[i + 1] * S], mem_ld, S, bounds[i + 1] - bounds[i], max_len,
                                    start_token_id, end_token_id,
-                                   constraints=cons.rows(bounds[i], bounds[i + 1]) if cons.active() else None)
+                                   constraints=cons.rows(bounds[i], bounds[i + 1]) if cons.active() else None,
+                                   kv_dtype=kv_dtype)
                   for i in range(G)]
         steps = max_len - 1
         if steps > 0:
@@ -589,7 +595,8 @@ class ImageToTextModel:
     def generate_beam_batch(self, images, start_token_id: int, end_token_id: int, max_len: int = 100,
                             beam_size: int = config.BEAM_SIZE, length_penalty: float = 0.0, return_all: bool = False,
                             use_graph: bool = True, check_every: int = 8, repetition_penalty: float = 1.0,
-                            no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=(), prompts=None):
+                            no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=(), prompts=None,
+                            kv_dtype: Optional[str] = None):
         """Beam-search captions for a whole batch: beam_size slots per image on the KV-cache step of
         generate_batch (decoder.beam_begin / beam_step). Per step a live beam offers its V continuations at
         score + log_softmax(logits), a finished beam itself once (padded); the beam_size best by (score, lower
@@ -606,7 +613,8 @@ class ImageToTextModel:
         repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts: the constraints of
         generate_batch (the defaults switch them off and leave the decode launch for launch what it was).
         A beam's constraints follow its own ids (its ancestry), scores are log_softmax of the constrained logits,
-        and a prompt adds nothing to a score."""
+        and a prompt adds nothing to a score. kv_dtype: as generate_batch (the beams of an image read its one
+        K/V, bf16 or fp8)."""
         self.eval()
         pv = images if isinstance(images, torch.Tensor) else \
             self.image_processor(images=images, return_tensors="pt")["pixel_values"]
@@ -616,7 +624,7 @@ class ImageToTextModel:
         dec = self.decoder
         cons = DecodeConstraints(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts)
         stt = dec.beam_begin(mem, mem_ld, S, B, K, max_len, start_token_id, end_token_id,
-                             constraints=cons if cons.active() else None)
+                             constraints=cons if cons.active() else None, kv_dtype=kv_dtype)
         steps = max_len - 1
         dec.beam_step(stt)  # position 0 (eager: warms every kernel before capture)
         done = 1
@@ -660,7 +668,8 @@ class ImageToTextModel:
                               temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_samples: int = 1,
                               seed: int = 0, image_offset: int = 0, return_logprob: bool = False,
                               use_graph: bool = True, check_every: int = 8, repetition_penalty: float = 1.0,
-                              no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=(), prompts=None):
+                              no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=(), prompts=None,
+                              kv_dtype: Optional[str] = None):
         """Sampled captions for a whole batch: num_samples rows per image on the KV-cache step of generate_batch
         (decoder.sample_begin / sample_step). Per step a live row draws its next token from softmax(logits /
         temperature) restricted to the top_k most likely tokens and, inside them, to the shortest prefix of mass
@@ -677,7 +686,8 @@ class ImageToTextModel:
 
         repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts: the constraints of
         generate_batch (the defaults switch them off and leave the decode launch for launch what it was).
-        The draw and the logprob are taken from the constrained logits; a prompt adds nothing to a logprob."""
+        The draw and the logprob are taken from the constrained logits; a prompt adds nothing to a logprob.
+        kv_dtype: as generate_batch (the samples of an image read its one K/V, bf16 or fp8)."""
         self.eval()
         pv = images if isinstance(images, torch.Tensor) else \
             self.image_processor(images=images, return_tensors="pt")["pixel_values"]
@@ -688,7 +698,7 @@ class ImageToTextModel:
         cons = DecodeConstraints(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts)
         stt = dec.sample_begin(mem, mem_ld, S, B, N, max_len, start_token_id, end_token_id, temperature=temperature,
                                top_k=top_k, top_p=top_p, seed=seed, row0=int(image_offset) * N,
-                               constraints=cons if cons.active() else None)
+                               constraints=cons if cons.active() else None, kv_dtype=kv_dtype)
         steps = max_len - 1
         dec.sample_step(stt)  # position 0 (eager: warms every kernel before capture)
         done = 1

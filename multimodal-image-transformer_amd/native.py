@@ -73,6 +73,8 @@ class DecodeGemmPlan(ctypes.Structure):
 
 # mit_attention_decode_plan
 DECODE_ATTN_BH, DECODE_ATTN_ROWS, DECODE_ATTN_ROWS_NT = 0, 1, 2
+# mit_attention_decode_fp8_plan
+DECODE_ATTN_FP8_BH, DECODE_ATTN_FP8_ROWS = 3, 4
 
 
 class LnGradsJob(ctypes.Structure):
@@ -184,6 +186,9 @@ SIGNATURES = {
     "mit_sample_pick": (I, [L, L, vp, L, Fl, L, Fl, vp, L, vp, vp, L, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp,
                             vp, vp, vp]),
     "mit_logits_constrain": (I, [L, L, vp, L, vp, L, vp, L, vp, L, vp, Fl, L, L, ctypes.c_int64, vp, L, vp, L, vp]),
+    "mit_kv_quantize_fp8": (I, [L, L, L, L, vp, L, L, vp, L, L, vp, vp]),
+    "mit_attention_decode_fp8": (I, [L, L, L, vp, L, vp, L, L, vp, L, L, vp, vp, L, vp, L, L, L, Fl, vp]),
+    "mit_attention_decode_fp8_plan": (I, [L, L, L, vp, L, vp, L, L, vp, L, L, vp, vp, L, vp, L, L, L]),
 }
 
 
@@ -916,6 +921,32 @@ def decode_layernorm(z, stats, gamma, beta, out, eps=1e-5):
     M, W = z.shape
     _check(lib().mit_decode_layernorm(M, W, ptr(z), z.stride(0), ptr(stats), ptr(gamma), ptr(beta), eps, ptr(out),
                                       out.stride(0), stream_ptr()), "mit_decode_layernorm")
+
+
+# --- FP8 cross-attention K/V (kv8.hip) ---------------------------------------------------------------
+def kv_quantize_fp8(src, s_row, s_batch, dst, d_row, d_batch, scales, B, S, G, *, Dh=64):
+    """dst (e4m3fn bytes, uint8) and scales (f32 [B, G], powers of two) <- the bf16 rows src: B images of S rows
+    of G groups of Dh columns, one scale per (image, group) (mit_kv_quantize_fp8; src strides in elements, dst
+    strides in bytes)."""
+    _check(lib().mit_kv_quantize_fp8(B, S, G, Dh, ptr(src), s_row, s_batch, ptr(dst), d_row, d_batch, ptr(scales),
+                                     stream_ptr()), "mit_kv_quantize_fp8")
+
+
+def attention_decode_fp8(q, q_batch, k, k_row, k_batch, v, v_row, v_batch, k_scale, v_scale, scale_batch, o, o_batch,
+                         R, H, *, Lk, group=1, scale=0.125, Dh=64):
+    """attention_decode's cross-attention (fixed Lk) over e4m3fn K / V bytes (strides in bytes) with per (image,
+    head) power-of-two scales; row r reads image r // group."""
+    _check(lib().mit_attention_decode_fp8(R, H, Dh, ptr(q), q_batch, ptr(k), k_row, k_batch, ptr(v), v_row, v_batch,
+                                          ptr(k_scale), ptr(v_scale), scale_batch, ptr(o), o_batch, Lk, group, scale,
+                                          stream_ptr()), "mit_attention_decode_fp8")
+
+
+def attention_decode_fp8_plan(R, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, k_scale, v_scale,
+                              scale_batch, o, o_batch, *, Lk, group=1) -> int:
+    """DECODE_ATTN_FP8_BH / _ROWS: the kernel family attention_decode_fp8 would launch (host only, no GPU needed);
+    -1 for rejected arguments. Pointers are integers (addresses) or None."""
+    return lib().mit_attention_decode_fp8_plan(R, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, k_scale,
+                                               v_scale, scale_batch, o, o_batch, Lk, group)
 
 
 # --- beam-search decoding (beam.hip) ---------------------------------------------------------------
