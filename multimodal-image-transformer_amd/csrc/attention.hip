@@ -476,6 +476,10 @@ constexpr int HK_MAX = 640;  // keys per head the LDS can hold (K + V = 256 B pe
 // softmax rescale (ViT-B/16 -0.3 us, CLIP-L -2.9 us, step neutral, but the cfg3 bf16 logits over the 1e-2
 // bound) and two 16-query tiles per wave (ViT-B/16 26.7 -> 30.6 us, decoder cross 8.8 -> 12.3 us).
 constexpr int HS = 4;
+// The dropout instance (decoder cross-attention, <= 4 waves at Lq <= 64) keeps 8: a 63 x 197 head is 6.5 chunk
+// rows of K and of V per thread, which HS = 4 fetched in two dependent round trips of cold, strided HBM rows
+// (the step's kv_all layout) before the first MFMA; 8 puts them all in flight at once.
+constexpr int HS_DROP = 8;
 
 // cross-lane reductions over the 4 lane groups of a 16-query tile (lanes l, l ^ 16, l ^ 32, l ^ 48
 // hold one query's key groups): v_permlane16_swap / v_permlane32_swap of a value with itself leave
@@ -506,6 +510,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, DROP ? 512 : 1024))) v
   extern __shared__ __attribute__((aligned(16))) char lds[];
   char* Ks = lds;
   char* Vs = lds + (long)lkp * 128;
+  constexpr int HSN = DROP ? HS_DROP : HS;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, nw = blockDim.x >> 6;
   const long h = blockIdx.x, b = blockIdx.y;
   MIT_DASSERT(h < H && Lk <= lkp && lkp <= HK_MAX && Lq > 0);
@@ -516,10 +521,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, DROP ? 512 : 1024))) v
   // stage K and V: 8 16-B chunks per row, HS rows of chunks per thread with all their loads in flight
   // before the first LDS write (one round trip per HS, not per chunk row)
   const int nid = lkp * 8;
-  for (int base = tid; base < nid; base += HS * (int)blockDim.x) {
-    u32x4 kv[HS], vv[HS];
+  for (int base = tid; base < nid; base += HSN * (int)blockDim.x) {
+    u32x4 kv[HSN], vv[HSN];
 #pragma unroll
-    for (int u = 0; u < HS; ++u) {
+    for (int u = 0; u < HSN; ++u) {
       const int id = base + u * (int)blockDim.x, r = id >> 3, c = id & 7;
       const bool ok = r < Lk;  // id >= nid gives r >= lkp >= Lk
       kv[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
@@ -528,7 +533,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, DROP ? 512 : 1024))) v
                                             rv, (int)(ok ? (uint32_t)((r * a.v_row + c * 8) * 2) : A_OOB), 0, 0));
     }
 #pragma unroll
-    for (int u = 0; u < HS; ++u) {
+    for (int u = 0; u < HSN; ++u) {
       const int id = base + u * (int)blockDim.x, r = id >> 3, c = id & 7;
       if (id < nid) {
         *(u32x4*)(Ks + koff_k(r, c)) = kv[u];
@@ -984,7 +989,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_mfma(long H, long Lq, long L
 //     tile in the K-tile swizzle (four 8-byte stores per strip and lane).
 //   phase B (waves over 16 queries x 32 head dims): dQ^T = K^T dS^T, both operands by transposed
 //     LDS reads of the K and dS^T tiles (the same permuted k order on both sides).
-// The dropout mask and exp are evaluated once per element (the split kernels evaluate both twice).
+// The dropout mask and exp are evaluated once per element (the split kernels evaluate both twice); the mask is
+// hashed into one bit per element while the batch of loads is in flight, and phase A only selects on the bit.
 // LDS: (2 * Lk + 128) rows x 128 B <= 80 KiB, so two workgroups share a CU (<= 128 VGPRs).
 // ------------------------------------------------------------------------------------------------
 constexpr int HB_MAXK = 256;  // keys per head
@@ -1011,6 +1017,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void a
   const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)Vb, (short)0, nb_.v, 0x00020000);
   // ---- one batch of loads ----
   bf16x8 vf[HB_SPW][2];  // B operand of dP = dO V^T for this wave's strips (key on the lane)
+  uint32_t mbits[HB_SPW] = {};
 #pragma unroll
   for (int si = 0; si < HB_SPW; ++si)
 #pragma unroll
@@ -1041,7 +1048,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void a
         u32x4, __builtin_amdgcn_raw_buffer_load_b128(rd, (int)(qok ? (uint32_t)((r * gr.do_row + ch * 8) * 2) : A_OOB), 0, 0));
     bf16x8 ov = {};
     if (qok) ov = *(const bf16x8*)(Ob + r * a.o_row + ch * 8);
-    const float l = (qok && ch == 0) ? a.lse[bh * Lq + r] : 0.f;
+    // every lane loads its row's lse (a live row's for the dead ones): a load under the (qok && ch == 0) branch
+    // was waited for inside the branch, with the whole batch above, before anything else could issue
+    const float l = a.lse[bh * Lq + (qok ? r : 0)];
+    // the lane's dropout mask bits of phase A (bit nb * 4 + t of strip si = query nb * 16 + g * 4 + t, key on the
+    // lane), hashed here: the hash needs no memory, and the batch of loads above is in flight until the LDS writes
+    // below wait for it. Index (bh * Lq + qq) * Lk + kl < 2^32 (host-checked).
+    if (a.dropout) {
+      const uint32_t kf = key_fold(site_key(a.seed, a.site));
+#pragma unroll
+      for (int si = 0; si < HB_SPW; ++si) {
+        const uint32_t i0 = ((uint32_t)bh * (uint32_t)Lq + (uint32_t)(g * 4)) * (uint32_t)Lk +
+                            (uint32_t)((w + 8 * si) * 16 + (lane & 15));
+        uint32_t bits = 0;
+        if ((w + 8 * si) * 16 < lkp) {  // wave-uniform
+#pragma unroll
+          for (int k = 0; k < 16; ++k)
+            bits |= (uint32_t)(lowbias32((i0 + (uint32_t)((k >> 2) * 16 + (k & 3)) * (uint32_t)Lk) ^ kf) >= a.thresh) << k;
+        }
+        mbits[si] = bits;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int c = tid + HB_NT * i;
@@ -1058,14 +1085,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void a
     dl += __shfl_xor(dl, 2, 64);
     dl += __shfl_xor(dl, 4, 64);
     if (ch == 0) {
-      Ls[r] = l * 1.4426950408889634f;
+      Ls[r] = qok ? l * 1.4426950408889634f : 0.f;
       Dl[r] = dl;
       if (qok) gr.delta[bh * Lq + r] = dl;
     }
   }
   __syncthreads();
   const float sl2 = a.scale * 1.4426950408889634f;
-  const uint64_t key = a.dropout ? site_key(a.seed, a.site) : 0ull;
   const int64_t* tok = a.tok ? a.tok + b * a.tok_batch : nullptr;
   typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
   // ---- phase A: key strips ----
@@ -1093,10 +1119,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void a
     }
     bf16x4 bp4[4], bs4[4];  // (P o M) and dS, 4 consecutive queries (t) per 16-query block nb
     const bool kdead = !klive || kpad;
-    // dropout index (bh * Lq + qq) * Lk + kl < 2^32 (host-checked): the lane's part once, then a wave-uniform
-    // step per (nb, t); drop_mul32 hashes it exactly as drop_mul does
-    const uint32_t ilane = ((uint32_t)bh * (uint32_t)Lq + (uint32_t)(g * 4)) * (uint32_t)Lk + (uint32_t)kl;
-    const uint32_t kf = key_fold(key);
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
       // the 4 queries' log-sum-exp and delta in one 16-B LDS read each (were 8 ds_read_b32)
@@ -1110,8 +1132,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void a
         // rescale per element, and the masked form compiled into exec-masked branches)
         const float e = __builtin_amdgcn_exp2f(s[nb][t] * sl2 - lq4[t]);
         const float p = msk ? 0.f : e;
-        const float mul =
-            a.dropout ? drop_mul32(kf, ilane + (uint32_t)(nb * 16 + t) * (uint32_t)Lk, a.thresh, a.dscale) : 1.f;
+        const float mul = a.dropout ? ((mbits[si] >> (nb * 4 + t)) & 1u ? a.dscale : 0.f) : 1.f;
         bp4[nb][t] = (bf16)(p * mul);
         bs4[nb][t] = (bf16)(p * (dp[nb][t] * mul - dl4[t]));
       }

@@ -1,6 +1,12 @@
 """Micro-benchmark of mit_attention_fwd on the train step's shapes (bf16, random operands):
 encoder MHSA (ViT-B/16: L=197, 12 heads; CLIP-L/14@336: L=577, 16 heads) and the decoder
-cross-attention (63 queries over 197 patches, 8 heads). Prints us and TFLOP/s (4*Lq*Lk*64/head)."""
+cross-attention (63 queries over 197 patches, 8 heads). Prints us and TFLOP/s (4*Lq*Lk*64/head).
+
+--cold adds the "cold strided" mode: the cross-attention K/V become views into one
+[B*S, L*2*d] buffer laid out as decoder.py's kv_all (L = 6 layers, a layer's K row is 128-byte pieces at a
+L*2*d row stride), a timed batch is one launch per layer (six launches on six layers' K/V, back to back as in
+the step), and a pass over 512 MB of unrelated memory sits between batches so that the operands come from
+HBM. Both the hot (back-to-back, same operands) and the cold figure (median batch / launches) are printed."""
 import os
 import sys
 
@@ -14,39 +20,74 @@ SHAPES = [("enc vit-b16", 64, 12, 197, 197), ("dec cross", 64, 8, 63, 197), ("en
           # the decoder cross-attention as trained (dropout 0.1) at configs[1] / [3] / [2] memory lengths
           ("dec cross drop", 64, 8, 63, 197, 0.1), ("cfg3 cross drop", 64, 12, 63, 257, 0.1),
           ("cfg2 cross drop", 64, 8, 63, 577, 0.1), ("cfg2 cross", 64, 8, 63, 577)]
+LAYERS = 6  # decoder layers sharing kv_all
 
 
-def run(iters=20):
+def timed(fn, iters, flush=None):
+    """us per call of fn: back-to-back mean (flush None) or the median of calls timed one by one behind a flush"""
+    if flush is None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters * 1e3
+    ts = []
+    for _ in range(iters):
+        flush.add_(1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1) * 1e3)
+    ts.sort()
+    return ts[len(ts) // 2]
+
+
+def run(iters=20, cold=False):
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(0)
     seed = torch.tensor([5], dtype=torch.int64, device=dev)
     only = os.environ.get("ATTN_SHAPES")
+    flush = torch.zeros(128 << 20, device=dev) if cold else None  # 512 MB, twice the 256 MB last-level cache
     for name, B, H, Lq, Lk, *drop in SHAPES:
         if only and name not in only.split(","):
             continue
         E = H * 64
-        qkv = torch.randn(B, max(Lq, Lk), 3 * E, generator=g).to(dev, torch.bfloat16)
         o = torch.empty(B, Lq, E, device=dev, dtype=torch.bfloat16)
         lse = torch.empty(B * H * Lq, device=dev)
-        T = max(Lq, Lk)
-        a = native.attn_args(qkv, 3 * E, T * 3 * E, qkv[..., E:], 3 * E, T * 3 * E, qkv[..., 2 * E:], 3 * E, T * 3 * E,
-                             o, E, Lq * E, lse=lse, scale=0.125, drop_p=drop[0] if drop else 0.0,
-                             seed=seed if drop else None, site=3)
+        kw = dict(lse=lse, scale=0.125, drop_p=drop[0] if drop else 0.0, seed=seed if drop else None, site=3)
+        if cold and "cross" in name:
+            q = torch.randn(B, Lq, E, generator=g).to(dev, torch.bfloat16)
+            kv = torch.randn(B * Lk, LAYERS * 2 * E, generator=g).to(dev, torch.bfloat16)
+            ld = LAYERS * 2 * E
+            args = [native.attn_args(q, E, Lq * E, kv[:, l * 2 * E:], ld, Lk * ld, kv[:, l * 2 * E + E:], ld, Lk * ld,
+                                     o, E, Lq * E, **kw) for l in range(LAYERS)]
+        else:
+            T = max(Lq, Lk)
+            qkv = torch.randn(B, T, 3 * E, generator=g).to(dev, torch.bfloat16)
+            args = [native.attn_args(qkv, 3 * E, T * 3 * E, qkv[..., E:], 3 * E, T * 3 * E, qkv[..., 2 * E:], 3 * E,
+                                     T * 3 * E, o, E, Lq * E, **kw)]
+
+        def fn(a=args[len(args) // 2]):
+            native.attention_fwd(native.BF16, B, H, Lq, Lk, a)
+
+        def batch():
+            for a in args:
+                fn(a)
         for _ in range(3):
-            native.attention_fwd(native.BF16, B, H, Lq, Lk, a)
+            fn()
         torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            native.attention_fwd(native.BF16, B, H, Lq, Lk, a)
-        e1.record()
-        torch.cuda.synchronize()
-        t = e0.elapsed_time(e1) / iters * 1e-3
+        t = timed(fn, iters) * 1e-6
         fl = 4.0 * B * H * Lq * Lk * 64
-        print(f"{name:14s} B={B:3d} H={H:2d} Lq={Lq:4d} Lk={Lk:4d}  {t * 1e6:8.1f} us  {fl / t / 1e12:7.1f} TFLOP/s",
-              flush=True)
+        line = f"{name:14s} B={B:3d} H={H:2d} Lq={Lq:4d} Lk={Lk:4d}  {t * 1e6:8.1f} us  {fl / t / 1e12:7.1f} TFLOP/s"
+        if cold:
+            line += f"  cold {timed(batch, iters, flush) / len(args):8.1f} us"
+        print(line, flush=True)
 
 
 if __name__ == "__main__":
     native.load_library()
-    run()
+    run(cold="--cold" in sys.argv[1:])

@@ -11,7 +11,7 @@ while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 $flags -c $SRC.hip -o build/variants/${SRC}_$name.o
   objs=""
-  for s in capi gemm norm attention misc decode image; do
+  for s in capi gemm norm attention misc decode beam sample constrain image kv8; do
     if [ $s = $SRC ]; then objs="$objs build/variants/${SRC}_$name.o"; else objs="$objs build/$s.o"; fi
   done
   /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 $objs -o ../lib/ab/libmit_hip_$name.so
