@@ -674,6 +674,50 @@ int mit_logits_constrain(long R, long V, float* logits, long ld, const int64_t* 
                          long n_suppress, const int64_t* forced, long ld_forced, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Caption scoring (csrc/score.hip; additive since ABI 9): the teacher-forced log-probability of a GIVEN target token
+ * per logits row, its rank in the row, and their per-sequence reduction -- the head of
+ * ImageToTextModel.score_captions, where the picks above answer "which token" and the cross-entropy answers "what
+ * loss over the batch".
+ *
+ * score_rows: for each row r < R of logits [R, V] (MIT_BF16 or MIT_F32, row stride ld), with t = targets[r] (int64)
+ *   and l_v = logits[r*ld + v]:
+ *   - t == ignore_index: token_logprob[r] = 0, rank[r] = -1; the logits row is never read (it may hold NaN);
+ *   - otherwise token_logprob[r] = l_t - lse(l) in f32, lse = m + log(sum_v exp(l_v - m)) with m the row maximum
+ *     (the form of mit_beam_select and mit_sample_pick), and rank[r] (int32) = the number of columns v < V with
+ *     l_v > l_t, or l_v == l_t and v < t: the position of t in the picks' order (logit descending, then token
+ *     ascending; integer compares on order-preserving keys, -0.0 == +0.0). rank == 0 exactly when torch.argmax of
+ *     the row is t; rank < k is top-k accuracy.
+ *   Columns >= V are never read or written (the ld padding may hold NaN); logits is never written; nothing but
+ *   token_logprob[0 .. R) and rank[0 .. R) is written. rank may be NULL (no count is made). A target outside [0, V)
+ *   that is not ignore_index is the caller's to reject (ImageToTextModel.score_captions does, on the host); here it
+ *   is undefined as in the cross-entropy contract: it never indexes the row, and the row's two outputs hold
+ *   unspecified values. A row with -inf columns is fine. A row whose maximum is -inf, or that holds a NaN in
+ *   [0, V), gives an undefined token_logprob (and rank), and nothing outside the row's two outputs is written.
+ *   1 <= V < 2^31; ld >= V; 0 <= R < 2^31; logits aligned to its element (2 B / 4 B), targets, token_logprob not
+ *   NULL. 16-B loads when logits is 16-B aligned and ld is a multiple of 8 (bf16) / 4 (f32); element loads
+ *   otherwise, with the same chunks per thread and the same summation order: the same result, bit for bit.
+ *   One 256-thread block per row. Two kernel families, chosen from (dtype, V) alone: MIT_SCORE_REGS for bf16 rows
+ *   with V <= 10240 (the row held in the block's registers: one read of the logits), MIT_SCORE_STREAM otherwise (a
+ *   second pass over the row for the sum of exponentials, served by the caches).
+ * mit_score_rows_plan: the family mit_score_rows would launch, from the same host decision function; -1 for
+ *   arguments it rejects (dtype, V, ld, R, logits NULL or misaligned). No launch, nothing dereferenced, no GPU needed.
+ * score_sequences: rows s*T .. s*T + T - 1 are sequence s < n_seq:
+ *     seq_logprob[s] = ((0 + token_logprob[s*T]) + token_logprob[s*T + 1]) + ...   (f32, in that order)
+ *     seq_tokens[s]  = #{j: rank[s*T + j] >= 0}    (int32: the rows that were scored)
+ *     seq_hits[s]    = #{j: rank[s*T + j] == 0}    (int32: the rows whose target is the row's argmax)
+ *   Outputs are overwritten; the inputs are not written. seq_tokens and seq_hits may be NULL; rank may be NULL when
+ *   both are. 0 <= n_seq < 2^31, 1 <= T < 2^31; token_logprob and seq_logprob not NULL.
+ * Both: arguments are checked before anything is recorded or launched; R == 0 / n_seq == 0 launches nothing.
+ * Asynchronous, recordable, capturable. Deterministic: no atomics, every sum in a fixed order; a second launch on the
+ * same inputs is bitwise equal. Pinned by tests/score_contract.py. */
+enum { MIT_SCORE_STREAM = 0, MIT_SCORE_REGS = 1 };
+int mit_score_rows_plan(int dtype, long R, long V, const void* logits, long ld);
+int mit_score_rows(int dtype, long R, long V, const void* logits, long ld, const int64_t* targets, int ignore_index,
+                   float* token_logprob, int* rank, void* stream);
+int mit_score_sequences(long n_seq, long T, const float* token_logprob, const int* rank, float* seq_logprob,
+                        int* seq_tokens, int* seq_hits, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * FP8 cross-attention K / V for the decode step (csrc/kv8.hip; additive since ABI 9, opt-in: the bf16 entry points
  * above are what a decode uses unless asked). The image memory's K | V rows, which every token step streams once,
  * stored as OCP e4m3fn bytes (never fnuz) with one power-of-two f32 scale per (image, head) for K and one for V.

@@ -205,6 +205,29 @@ class _Acts:
             self.gws_kv = None  # the cross-K/V weight gradient alone (TransformerDecoder.kv_dw_early)
 
 
+SCORE_LOGITS_BYTES = 32 << 20  # budget of run_score's head buffer (head_rows x Vp logits in the model dtype)
+
+
+class _ScoreActs:
+    """Activation arena of run_score for one (B, C, T, S, head_rows) shape: forward-only buffers over the
+    B * C * T candidate rows, the cross-attention K/V of the B images, ONE head chunk of logits, and the scores."""
+
+    def __init__(self, B, C, T, S, d, F, L, Vp, H, dt, dev, head_rows):
+        R = B * C * T
+        e = lambda *s: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+        i = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)  # noqa: E731
+        self.R, self.head_rows = R, head_rows
+        self.x0, self.y = e(R, d), e(R, d)
+        self.kv = e(B * S, L * 2 * d)
+        self.qkv, self.os, self.oc, self.qc, self.h = e(R, 3 * d), e(R, d), e(R, d), e(R, d), e(R, F)
+        self.xs = [[e(R, d) for _ in range(3)] for _ in range(2)]
+        self.lse = f(B * C * H * T)
+        self.logits = e(head_rows, Vp)
+        self.token_logprob, self.rank = f(R), i(R)
+        self.seq_logprob, self.seq_tokens, self.seq_hits = f(B * C), i(B * C), i(B * C)
+
+
 class _SideStream:
     """Second HIP stream for the backward's weight-gradient GEMMs (dW = dY^T X). Each layer's dW
     and dX GEMMs are independent; at d = 512 a decoder GEMM fills only 128-512 of the CUs' 512
@@ -629,6 +652,87 @@ class TransformerDecoder:
         logits = A.logits if logits_out is None else logits_out
         native.linear(xin, w("fc_out.weight"), logits, bias=st.p("fc_out.bias"))
         return logits, xin
+
+    # --- scoring -----------------------------------------------------------------------------
+    def default_head_rows(self, R: int) -> int:
+        """Rows per head chunk of run_score: as many as keep the head_rows x Vp logits buffer within
+        SCORE_LOGITS_BYTES (32 MiB: 1536 rows of the bf16 V = 10000 head, a 6 x 40 grid of 256-tiles), a multiple
+        of 256 where that is possible, and never more than the R rows there are."""
+        n = max(1, SCORE_LOGITS_BYTES // (self.Vp * torch.empty(0, dtype=self.dtype).element_size()))
+        if n >= 256:
+            n -= n % 256
+        return max(1, min(n, R))
+
+    def score_acts(self, B, C, T, S, head_rows) -> _ScoreActs:
+        key = ("score", B, C, T, S, head_rows)
+        if key not in self._acts:
+            self._acts[key] = _ScoreActs(B, C, T, S, self.d, self.F, self.L, self.Vp, self.H, self.dtype, self.device,
+                                         head_rows)
+        return self._acts[key]
+
+    def run_score(self, tokens: torch.Tensor, targets: torch.Tensor, mem: torch.Tensor, mem_ld: int, S: int, *,
+                  head_rows: Optional[int] = None) -> _ScoreActs:
+        """Teacher-forced scores of C candidate captions per image: tokens / targets int64 [B, C, T] (device; the
+        decoder inputs and the tokens they should predict, pad_idx = not scored); mem: memory rows [B*S, d] with
+        row stride mem_ld. Forward only, no dropout, and nothing is kept for a backward.
+
+        The image's cross-attention K/V is computed once for its C candidates (one GEMM over B*S rows); the
+        self-attention runs over B*C sequences of T (causal + key-padding from tokens, as run_forward), the
+        cross-attention as B batches of C*T queries over the image's S keys (q/o batch stride C*T*d), everything
+        else row-wise over the B*C*T rows. The vocabulary head runs head_rows rows at a time (default:
+        default_head_rows) into one logits buffer that native.score_rows reduces to a log-probability and a rank
+        per row before the next chunk overwrites it, so logits for all rows never exist; native.score_sequences
+        then sums per candidate. A chunk need not be a multiple of T. No GEMM takes a split-K workspace: a row's
+        values do not depend on how many rows the call has.
+
+        Returns the arena: seq_logprob f32 / seq_tokens / seq_hits int32 [B*C], token_logprob f32 / rank int32
+        [B*C*T] (views the next call with the same shape overwrites)."""
+        B, C, T = tokens.shape
+        d, H, L, V = self.d, self.H, self.L, self.V
+        st = self.store
+        w = st.w
+        R = B * C * T
+        hr = self.default_head_rows(R) if head_rows is None else int(head_rows)
+        if hr < 1:
+            raise ValueError(f"head_rows must be positive, got {head_rows}")
+        hr = min(hr, R)
+        A = self.score_acts(B, C, T, S, hr)
+        tok2 = tokens.view(B * C, T)
+        tgt = targets.view(R)
+        dt = native.dtype_code(A.x0)
+        scale = 1.0 / math.sqrt(self.hd)
+        native.gemm(mem, w("cross_kv.weight"), A.kv, B * S, L * 2 * d, d, lda=mem_ld, bias=st.p("cross_kv.bias"))
+        native.embed_fwd(tok2, w("token_embedding.weight"), math.sqrt(d), self.pe, A.x0)
+        xin = A.x0
+        for l in range(L):
+            xs = A.xs[l % 2]
+            pre = f"layers.{l}."
+            native.linear(xin, w(pre + "self_in.weight"), A.qkv, bias=st.p(pre + "self_in.bias"))
+            sa = native.attn_args(A.qkv, 3 * d, T * 3 * d, A.qkv[:, d:], 3 * d, T * 3 * d, A.qkv[:, 2 * d:], 3 * d,
+                                  T * 3 * d, A.os, d, T * d, lse=A.lse, key_tokens=tok2, tok_batch=T,
+                                  pad_idx=self.pad_idx, causal=True, scale=scale)
+            native.attention_fwd(dt, B * C, H, T, T, sa, Dh=self.hd)
+            native.linear(A.os, w(pre + "self_out.weight"), A.y, bias=st.p(pre + "self_out.bias"))
+            native.layernorm_fwd(xin, st.p(pre + "norm1.weight"), st.p(pre + "norm1.bias"), 1e-5, xs[0], r=A.y)
+            native.linear(xs[0], w(pre + "cross_q.weight"), A.qc, bias=st.p(pre + "cross_q.bias"))
+            kvl = A.kv[:, l * 2 * d:]
+            ca = native.attn_args(A.qc, d, C * T * d, kvl, L * 2 * d, S * L * 2 * d, kvl[:, d:], L * 2 * d,
+                                  S * L * 2 * d, A.oc, d, C * T * d, lse=A.lse, scale=scale)
+            native.attention_fwd(dt, B, H, C * T, S, ca, Dh=self.hd)
+            native.linear(A.oc, w(pre + "cross_out.weight"), A.y, bias=st.p(pre + "cross_out.bias"))
+            native.layernorm_fwd(xs[0], st.p(pre + "norm2.weight"), st.p(pre + "norm2.bias"), 1e-5, xs[1], r=A.y)
+            native.linear(xs[1], w(pre + "linear1.weight"), A.h, bias=st.p(pre + "linear1.bias"), act=native.ACT_RELU)
+            native.linear(A.h, w(pre + "linear2.weight"), A.y, bias=st.p(pre + "linear2.bias"))
+            native.layernorm_fwd(xs[1], st.p(pre + "norm3.weight"), st.p(pre + "norm3.bias"), 1e-5, xs[2], r=A.y)
+            xin = xs[2]
+        wo, bo = w("fc_out.weight"), st.p("fc_out.bias")
+        for r0 in range(0, R, hr):
+            n = min(hr, R - r0)
+            native.linear(xin[r0:r0 + n], wo, A.logits, bias=bo)
+            native.score_rows(A.logits, tgt[r0:r0 + n], self.pad_idx, A.token_logprob[r0:r0 + n], A.rank[r0:r0 + n],
+                              rows=n, V=V, ld=self.Vp)
+        native.score_sequences(A.token_logprob, A.rank, T, A.seq_logprob, A.seq_tokens, A.seq_hits, n_seq=B * C)
+        return A
 
     def run_backward(self, tokens: torch.Tensor, mem: torch.Tensor, mem_ld: int, S: int, A: _Acts,
                      seed: Optional[torch.Tensor], dlogits: torch.Tensor,

@@ -10,6 +10,7 @@ post-processing so a batch yields the reference's caption for every image.
 from __future__ import annotations
 
 import argparse
+import json
 import os
 from typing import Callable, List, Optional, Sequence
 
@@ -125,6 +126,41 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
     return out
 
 
+def rank_scores(logprobs: Sequence[float], tokens: Sequence[int], length_penalty: float = 0.0):
+    """One image's candidates, best first: (candidate index, logprob, tokens, logprob / tokens**length_penalty),
+    ordered by the last entry descending, ties to the lower index (model.rank_beams' rule)."""
+    rows = [(c, float(lp), int(n), float(lp) / max(int(n), 1) ** length_penalty)
+            for c, (lp, n) in enumerate(zip(logprobs, tokens))]
+    return sorted(rows, key=lambda r: (-r[3], r[0]))
+
+
+def score_captions(model, images, candidates, batch_size: int = 256, length_penalty: float = 0.0, *,
+                   start_token_id: int = config.START_TOKEN_ID, end_token_id: int = config.END_TOKEN_ID):
+    """Rank given candidate captions per image by the model's teacher-forced log-likelihood
+    (ImageToTextModel.score_captions). images: PIL images / HWC arrays or a [B,3,H,W] pixel tensor, `batch_size`
+    images per call, as generate_captions batches them. candidates: one flat list of candidate id lists scored
+    against every image (zero-shot classification by prompt, retrieval), or one such list per image (re-ranking
+    an image's own samples), or an int64 [B, C, L] tensor padded with PAD; a list or tensor per image is cut with
+    the images. Returns per image rank_scores' list, best first. A candidate's score does not depend on which
+    images share its batch."""
+    if isinstance(images, torch.Tensor):
+        pv = images if images.dim() == 4 else images.unsqueeze(0)
+    else:
+        pv = model.image_processor(images=list(images), return_tensors="pt")["pixel_values"]
+    per_image = isinstance(candidates, torch.Tensor) or \
+        any(len(c) > 0 and isinstance(c[0], (list, tuple)) for c in candidates)
+    if per_image and len(candidates) != pv.shape[0]:
+        raise ValueError(f"score_captions: {len(candidates)} candidate lists for {pv.shape[0]} images")
+    out = []
+    for i in range(0, pv.shape[0], batch_size):
+        chunk = pv[i:i + batch_size].to(model.device).float()
+        cand = candidates[i:i + batch_size] if per_image else candidates
+        lp, n, _ = model.score_captions(chunk, cand, start_token_id, end_token_id)
+        for lps, ns in zip(lp.tolist(), n.tolist()):
+            out.append(rank_scores(lps, ns, length_penalty))
+    return out
+
+
 def generate_caption(image, model, decode=None) -> str:
     """inference.py:17-128 for one image (path, PIL image or pixel tensor) with a loaded model."""
     if isinstance(image, str):
@@ -168,7 +204,19 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--kv_dtype", choices=["bf16", "fp8"], default=None,
                     help="storage of the cross-attention K/V: fp8 halves its memory and the bytes a token step streams "
                          "(bf16 checkpoints; default: env MIT_DECODE_KV, else bf16)")
+    ap.add_argument("--score_file", default=None,
+                    help="score instead of generating: a JSON file holding one list of candidate id lists (scored "
+                         "against every image) or one such list per image; prints each image's ranking")
     return ap
+
+
+def load_score_file(path: str):
+    """The candidates of --score_file: a JSON list of candidate id lists, or a list of such lists (one per image)."""
+    with open(path) as f:
+        cands = json.load(f)
+    if not isinstance(cands, list) or not cands or not all(isinstance(c, list) for c in cands):
+        raise ValueError(f"{path}: expected a JSON list of candidate id lists, or one such list per image")
+    return cands
 
 
 def decode_options(args) -> dict:
@@ -196,12 +244,22 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.temperature is not None and args.beam_size is not None:
         ap.error("--beam_size and --temperature exclude each other")
+    if args.score_file is not None and (args.temperature is not None or args.beam_size is not None):
+        ap.error("--score_file scores given captions: it excludes --beam_size and --temperature")
     from PIL import Image
     model = load_model(args.checkpoint_path)
     for p in args.image_path:
         if not os.path.exists(p):
             raise FileNotFoundError(f"Image file not found: {p}")
     ims = [Image.open(p).convert("RGB") for p in args.image_path]
+    if args.score_file is not None:
+        ranked = score_captions(model, ims, load_score_file(args.score_file), batch_size=args.batch_size,
+                                length_penalty=args.length_penalty)
+        for p, rows in zip(args.image_path, ranked):
+            print(f"{p}:")
+            for c, lp, n, s in rows:
+                print(f"  candidate {c}: logprob {lp:.4f} over {n} tokens, score {s:.4f}")
+        return
     for p, (ids, text) in zip(args.image_path, generate_captions(model, ims, _tokenizer_decode(),
                                                                   **decode_options(args))):
         print(f"{p}: {text if text is not None else ids}")

@@ -452,6 +452,118 @@ class ImageToTextModel:
         native.scalar_div(A.loss_sum, A.count, A.loss)
         return A.loss
 
+    # --- scoring -------------------------------------------------------------------------------
+    def _caption_sequences(self, captions, B: int, start_token_id: int, end_token_id: int) -> torch.Tensor:
+        """The candidates of score_captions as one int64 [B, C, L] CPU tensor of START .. END sequences padded with
+        pad_idx; every check of the candidates happens here, on the host, before anything is launched."""
+        pad, V = self.decoder_pad_idx, self.decoder.V
+        start, end = int(start_token_id), int(end_token_id)
+        min_len = 0
+        if isinstance(captions, torch.Tensor):
+            if captions.dim() != 3 or captions.shape[0] != B:
+                raise ValueError(f"score_captions: a caption tensor must be [B, C, L] with B = {B}, got "
+                                 f"{tuple(captions.shape)}")
+            min_len = captions.shape[2]
+            cap = captions.to("cpu", torch.int64)
+            if min_len >= 2 and min_len - 1 <= self.decoder.max_seq_len and 0 <= start < V and 0 <= end < V:
+                # whole START .. END sequences (a tokenised validation set): checked without a Python loop
+                n = (cap != pad).long().cumsum(-1).argmax(-1, keepdim=True)  # index of the last non-PAD id
+                if bool(((cap >= 0) & (cap < V)).all()) and bool((cap[..., :1] == start).all()) and \
+                        bool((cap.gather(-1, n) == end).all()) and cap.shape[1] > 0 and \
+                        bool(((cap != pad) | (torch.arange(min_len) > n)).all()):
+                    return cap.contiguous()
+            per = cap.tolist()
+            for img in per:  # a padded row holds its candidate up to the last non-PAD id
+                for c in img:
+                    while c and c[-1] == pad:
+                        c.pop()
+        else:
+            captions = list(captions)
+            if any(len(c) > 0 and isinstance(c[0], (list, tuple)) for c in captions):
+                if len(captions) != B:
+                    raise ValueError(f"score_captions: {len(captions)} candidate lists for {B} images")
+                per = [list(img) for img in captions]
+            else:  # one flat list of candidates for every image
+                per = [captions] * B
+        C = len(per[0]) if per else 0
+        if C == 0 or any(len(img) != C for img in per):
+            raise ValueError("score_captions: every image needs the same number (one at least) of candidates")
+        seqs = []
+        for b, img in enumerate(per):
+            for c, cand in enumerate(img):
+                ids = [int(t) for t in cand]
+                if not ids:
+                    raise ValueError(f"score_captions: candidate {c} of image {b} is empty")
+                if min(ids) < 0 or max(ids) >= V:
+                    raise ValueError(f"score_captions: candidate {c} of image {b} holds an id outside [0, {V})")
+                if ids[0] != start:
+                    ids = [start] + ids
+                if ids[-1] != end:
+                    ids = ids + [end]
+                seqs.append(ids)
+        if not (0 <= start < V and 0 <= end < V):
+            raise ValueError(f"score_captions: START / END ids outside [0, {V})")
+        L = max(min_len, max(len(s) for s in seqs))
+        if L - 1 > self.decoder.max_seq_len:
+            raise ValueError(f"score_captions: a sequence of {L} ids gives {L - 1} decoder positions, more than "
+                             f"max_seq_len = {self.decoder.max_seq_len}")
+        return torch.tensor([s + [pad] * (L - len(s)) for s in seqs], dtype=torch.int64).view(B, C, L)
+
+    @torch.no_grad()
+    def score_captions(self, images, captions, start_token_id: int, end_token_id: int, *, return_tokens: bool = False,
+                       head_rows: Optional[int] = None):
+        """Teacher-forced log-likelihoods of GIVEN captions, C candidates per image (the opposite question to
+        generate_*: how likely is this caption for this image). captions: a list per image of C candidate id
+        lists (ragged lengths; the same C for every image), or one flat list of candidates scored against every
+        image, or an int64 tensor [B, C, L] padded with pad_idx. A candidate without a leading START or a trailing
+        END gets them (what inference.postprocess_ids strips); the sequences are padded to a common length L, the
+        decoder reads seq[:-1] and is scored on seq[1:] (train.py's split), PAD targets are not scored.
+
+        The image is encoded once and its cross-attention K/V computed once for its C candidates; the vocabulary
+        head runs in chunks of head_rows rows, each reduced on the device to a log-probability and a rank per row
+        (csrc/score.hip), so logits [B, C, L - 1, V] never exist (decoder.run_score).
+
+        Returns device tensors (logprob f32 [B, C] = sum over the scored positions of log p(target), tokens int32
+        [B, C] = the scored positions, hits int32 [B, C] = the positions whose target is the argmax); with
+        return_tokens also (token_logprob f32 [B, C, L - 1], rank int32 [B, C, L - 1]: 0 = the target is the
+        argmax, rank < k = in the top k, -1 = PAD target). Empty candidates, ids outside [0, V), unequal candidate
+        counts and sequences with more than max_seq_len positions raise ValueError before anything is launched."""
+        n = images.shape[0] if isinstance(images, torch.Tensor) else len(images)
+        seq = self._caption_sequences(captions, n, start_token_id, end_token_id)
+        pv = images if isinstance(images, torch.Tensor) else \
+            self.image_processor(images=images, return_tensors="pt")["pixel_values"]
+        pv = pv.to(self.device).float()
+        seq = seq.to(self.device)
+        return self.score_tokens(pv, seq[:, :, :-1], seq[:, :, 1:], return_tokens=return_tokens, head_rows=head_rows)
+
+    @torch.no_grad()
+    def score_tokens(self, images: torch.Tensor, decoder_input_tokens: torch.Tensor, target_tokens: torch.Tensor, *,
+                     return_tokens: bool = False, head_rows: Optional[int] = None):
+        """score_captions on sequences that are already split and padded: pixel values [B, 3, H, W], decoder inputs
+        and targets int64 [B, C, T] (or [B, T]: one candidate per image, a train / validation batch as it is),
+        PAD targets not scored. Returns what score_captions returns, [B, C] (or [B])."""
+        tokens = decoder_input_tokens.to(self.device, torch.int64)
+        targets = target_tokens.to(self.device, torch.int64)
+        flat = tokens.dim() == 2
+        if flat:
+            tokens, targets = tokens.unsqueeze(1), targets.unsqueeze(1)
+        if tokens.dim() != 3 or tokens.shape != targets.shape or tokens.shape[0] != images.shape[0]:
+            raise ValueError(f"score_tokens: tokens {tuple(tokens.shape)} / targets {tuple(targets.shape)} do not match "
+                             f"{images.shape[0]} images")
+        B, C, T = tokens.shape
+        if T < 1 or T > self.decoder.max_seq_len:
+            raise ValueError(f"score_tokens: {T} decoder positions outside 1 .. max_seq_len = {self.decoder.max_seq_len}")
+        if head_rows is not None and int(head_rows) < 1:
+            raise ValueError(f"score_tokens: head_rows must be positive, got {head_rows}")
+        tokens, targets = tokens.contiguous(), targets.contiguous()
+        mem, mem_ld, S, _, _ = self._encode_memory(images.to(self.device))
+        A = self.decoder.run_score(tokens, targets, mem, mem_ld, S, head_rows=head_rows)
+        shape = (B,) if flat else (B, C)
+        out = (A.seq_logprob.view(shape).clone(), A.seq_tokens.view(shape).clone(), A.seq_hits.view(shape).clone())
+        if return_tokens:
+            out += (A.token_logprob.view(*shape, T).clone(), A.rank.view(*shape, T).clone())
+        return out
+
     # --- generate (model.py:171-255) -----------------------------------------------------------
     @torch.no_grad()
     def generate(self, image, start_token_id, end_token_id, max_len=100, method="greedy", beam_size=3) -> List[int]:

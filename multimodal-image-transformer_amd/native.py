@@ -111,6 +111,7 @@ class LnPlan(ctypes.Structure):
 LN_SCALAR, LN_VEC4, LN_WIDE, LN_PAIR = 0, 1, 2, 3
 CE_BLOCK, CE_ROWS = 0, 1      # mit_cross_entropy_plan
 ELT_SCALAR, ELT_VEC8 = 0, 1   # mit_im2col_plan / mit_vit_assemble_plan
+SCORE_STREAM, SCORE_REGS = 0, 1  # mit_score_rows_plan
 
 
 # name -> (restype, argtypes); mirrors include/mit_hip.h one to one
@@ -186,6 +187,9 @@ SIGNATURES = {
     "mit_sample_pick": (I, [L, L, vp, L, Fl, L, Fl, vp, L, vp, vp, L, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp,
                             vp, vp, vp]),
     "mit_logits_constrain": (I, [L, L, vp, L, vp, L, vp, L, vp, L, vp, Fl, L, L, ctypes.c_int64, vp, L, vp, L, vp]),
+    "mit_score_rows_plan": (I, [I, L, L, vp, L]),
+    "mit_score_rows": (I, [I, L, L, vp, L, vp, I, vp, vp, vp]),
+    "mit_score_sequences": (I, [L, L, vp, vp, vp, vp, vp, vp]),
     "mit_kv_quantize_fp8": (I, [L, L, L, L, vp, L, L, vp, L, L, vp, vp]),
     "mit_attention_decode_fp8": (I, [L, L, L, vp, L, vp, L, L, vp, L, L, vp, vp, L, vp, L, L, L, Fl, vp]),
     "mit_attention_decode_fp8_plan": (I, [L, L, L, vp, L, vp, L, L, vp, L, L, vp, vp, L, vp, L, L, L]),
@@ -1016,6 +1020,31 @@ def logits_constrain(logits, V, tok, pos, *, group=1, anc=None, finished=None, r
                                       int(end_id), ptr(suppress), suppress.numel() if suppress is not None else 0,
                                       ptr(forced), forced.stride(0) if forced is not None else 0, stream_ptr()),
            "mit_logits_constrain")
+
+
+def score_rows_plan(dtype, R, V, logits, ld) -> int:
+    """SCORE_REGS (bf16, V <= 10240: the row in registers) / SCORE_STREAM: the kernel score_rows would launch (host
+    only); -1 for rejected arguments"""
+    return lib().mit_score_rows_plan(dtype, R, V, ptr(logits), ld)
+
+
+def score_rows(logits, targets, ignore_index, token_logprob, rank=None, *, rows=None, V=None, ld=None):
+    """token_logprob[r] (f32) = log_softmax(logits[r, :V])[targets[r]] and rank[r] (int32, may be None) = the
+    number of columns ahead of the target in the picks' order (0: the target is the row's argmax); rows whose
+    target is ignore_index get 0 and -1 and are never read (mit_score_rows). logits [rows, ld] bf16 or f32."""
+    V = V if V is not None else logits.shape[-1]
+    rows = rows if rows is not None else targets.numel()
+    _check(lib().mit_score_rows(dtype_code(logits), rows, V, ptr(logits), ld if ld is not None else logits.stride(0),
+                                ptr(targets), ignore_index, ptr(token_logprob), ptr(rank), stream_ptr()),
+           "mit_score_rows")
+
+
+def score_sequences(token_logprob, rank, T, seq_logprob, seq_tokens=None, seq_hits=None, n_seq=None):
+    """Per sequence of T consecutive rows: the f32 sum of token_logprob in row order, the rows with rank >= 0 and
+    the rows with rank == 0 (mit_score_sequences); the outputs are overwritten."""
+    n_seq = n_seq if n_seq is not None else token_logprob.numel() // T
+    _check(lib().mit_score_sequences(n_seq, T, ptr(token_logprob), ptr(rank), ptr(seq_logprob), ptr(seq_tokens),
+                                     ptr(seq_hits), stream_ptr()), "mit_score_sequences")
 
 
 def image_normalize(src_u8, dst, mean, std):

@@ -160,6 +160,28 @@ def evaluate(model, dataloader, criterion, device):
     return (total / max(n, 1)).item()
 
 
+@torch.no_grad()
+def evaluate_metrics(model, dataloader) -> dict:
+    """Validation metrics from the scoring path (ImageToTextModel.score_tokens): {"loss": -sum of the target
+    log-probabilities / the non-PAD targets of the WHOLE set (evaluate averages per-batch means, as the reference
+    does, which weighs a short last batch like a full one), "perplexity": exp(loss), "token_accuracy": the share of
+    targets that are the argmax of their position, "tokens": the non-PAD targets}. The sums are taken in float64 on
+    the device, one synchronisation at the end."""
+    was_training = model.training
+    model.eval()
+    tot = torch.zeros(3, dtype=torch.float64, device=model.device)
+    for batch in _staged(model, dataloader):
+        lp, n, hits = model.score_tokens(batch["images"], batch["decoder_input_tokens"], batch["target_tokens"])
+        tot += torch.stack([lp.double().sum(), n.double().sum(), hits.double().sum()])
+    model.train(was_training)
+    lp, n, hits = tot.tolist()
+    if not n:
+        return {"loss": float("nan"), "perplexity": float("nan"), "token_accuracy": float("nan"), "tokens": 0}
+    loss = -lp / n
+    return {"loss": loss, "perplexity": math.exp(loss) if loss < 700 else float("inf"), "token_accuracy": hits / n,
+            "tokens": int(n)}
+
+
 class LinearWarmup:
     """transformers.get_linear_schedule_with_warmup semantics (train.py:331-341)."""
 
