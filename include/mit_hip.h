@@ -468,6 +468,60 @@ int mit_greedy_pick_advance(long B, long V, const float* logits, long ld, int64_
 int mit_greedy_pick_keys(long B, unsigned long long* keys, int64_t* ids, long ld_ids, int64_t* pos, int64_t end_id,
                          int64_t pad_id, int* finished, int* n_finished, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Rolling-batch decode (csrc/decode.hip, csrc/rolling.hip): the entry points above with one position PER ROW,
+ * row_pos (int64 [B] on the device) where they take the device scalar pos, so that the rows of one token step
+ * sit at different lengths and a finished row's slot can be handed to the next image (mit_slot_admit) while the
+ * others go on. All asynchronous on `stream`, recordable (mit_plan_*), deterministic; every row_pos[b] must lie
+ * in [0, rows of the caches / columns of ids / rows of pe) -- it is trusted as pos is.
+ * attention_decode_ragged: mit_attention_decode with Lk_b = row_pos[b] + 1 for row b (row_pos != NULL; with
+ *   row_pos == NULL the fixed Lk, launch for launch the scalar entry point's). Same arguments, alignment rules,
+ *   masks and kernel families (Lk is uniform over a block in both); row b's result is bitwise what
+ *   mit_attention_decode gives for that row alone with *pos = row_pos[b]. Tokens, K and V rows at j > row_pos[b]
+ *   are never read; row_pos and key_tokens are not written. mit_attention_decode_ragged_plan: the family, which is
+ *   the one mit_attention_decode_plan returns for the same arguments; -1 for rejected arguments; host only.
+ * kv_store_ragged: cache[b*c_batch + row_pos[b]*c_row + e] = src[b*s_batch + e], e < n; nothing else of the
+ *   cache is written.
+ * embed_decode_ragged: out[b, :] = table[ids[b*ld_ids + row_pos[b]]] * scale + pe[row_pos[b]]; ids columns other
+ *   than row_pos[b] of row b are not read.
+ * greedy_pick_ragged (f32 logits, mit_greedy_pick's argmax order: first maximum, NaN largest, -0.0 == +0.0) and
+ * greedy_pick_keys_ragged (the head's argmax keys, mit_greedy_pick_keys' decoding) share one rule. done (int32 [B]),
+ *   limit (int64 [B], 1 <= limit[b] <= ld_ids) and the int32 counter n_done replace finished / n_finished; no PAD is
+ *   written. A row with done[b] == 0 and p = row_pos[b]: ids[b*ld_ids + p + 1] = pick, row_pos[b] = p + 1, and when
+ *   the pick is end_id or p + 2 == limit[b] (the row is full) done[b] = 1 and *n_done += 1, once. A row with
+ *   done[b] != 0 is FROZEN: its ids, row_pos, done are not written and it is not counted (greedy_pick_ragged does not
+ *   read its logits); greedy_pick_keys_ragged still resets the keys of every row to 0. Hence row_pos[b] <= limit[b]
+ *   - 1 always: a frozen row that is stepped again rereads its last token, rewrites the same cache row with the same
+ *   values and attends at most limit[b] keys. A row that is not done with no room left (p + 1 >= limit[b]; never
+ *   reached from mit_slot_admit with cap >= 2) writes nothing and is retired. ids columns other than p + 1, limit,
+ *   and logits are not written.
+ * slot_admit: m admissions in one launch. triples: int64 [m][3] on the device, (slot, pool image, cap), slots
+ *   distinct, 0 <= slot < slots, 0 <= image < pool_images (a triple outside these copies and resets nothing),
+ *   2 <= cap <= ld_ids. For each: the image's S rows of row_bytes bytes of each of the L layers, pool_kv
+ *   [L][pool_images*S][row_bytes] -> kv [L][slots*S][row_bytes] (bf16 K|V rows or e4m3 bytes: plain bytes, 16-B
+ *   words; row_bytes % 16 == 0, both bases 16-B aligned); with scale != NULL also the image's n_scale floats per
+ *   layer, pool_scale [L][pool_images][n_scale] -> scale [L][slots][n_scale]; ids[slot*ld_ids] = start_id,
+ *   row_pos[slot] = 0, done[slot] = 0, limit[slot] = cap, *n_done -= 1 (m in all; a triple that is out of range is not counted). Slots not named, ids columns other than 0
+ *   and the pool are not written. m = 0 launches nothing; m <= slots, m and L < 65536. */
+int mit_attention_decode_ragged_plan(int dtype, long B, long H, long Dh, const void* q, long q_batch, const void* k,
+                                     long k_row, long k_batch, const void* v, long v_row, long v_batch, const void* o,
+                                     long o_batch, long Lk, const int64_t* row_pos, const int64_t* key_tokens);
+int mit_attention_decode_ragged(int dtype, long B, long H, long Dh, const void* q, long q_batch, const void* k, long k_row,
+                                long k_batch, const void* v, long v_row, long v_batch, void* o, long o_batch, long Lk,
+                                const int64_t* row_pos, const int64_t* key_tokens, long tok_batch, int pad_idx,
+                                float scale, void* stream);
+int mit_kv_store_ragged(int dtype, long B, long n, const void* src, long s_batch, void* cache, long c_row, long c_batch,
+                        const int64_t* row_pos, void* stream);
+int mit_embed_decode_ragged(int dtype, long B, long d, const int64_t* ids, long ld_ids, const int64_t* row_pos,
+                            const void* table, float scale, const float* pe, void* out, void* stream);
+int mit_greedy_pick_ragged(long B, long V, const float* logits, long ld, int64_t* ids, long ld_ids, int64_t* row_pos,
+                           int64_t end_id, const int64_t* limit, int* done, int* n_done, void* stream);
+int mit_greedy_pick_keys_ragged(long B, unsigned long long* keys, int64_t* ids, long ld_ids, int64_t* row_pos,
+                                int64_t end_id, const int64_t* limit, int* done, int* n_done, void* stream);
+int mit_slot_admit(long m, const int64_t* triples, long L, long S, long row_bytes, const void* pool_kv, long pool_images,
+                   void* kv, long slots, const float* pool_scale, float* scale, long n_scale, int64_t* ids, long ld_ids,
+                   int64_t start_id, int64_t* row_pos, int* done, int64_t* limit, int* n_done, void* stream);
+
 /* Decode-step GEMM with the decoder's post-LN residual blocks folded in (bf16 only; the B-row GEMMs of
  * one token step, torch/nn/modules/transformer.py:1144-1153 norm_first=False):
  *   C[M, N] = act(A'[M, K] . B[N, K]^T + bias) (+ residual),  B = bf16 weights (nn.Linear layout)

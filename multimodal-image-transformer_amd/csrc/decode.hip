@@ -21,7 +21,8 @@ namespace {
 
 // head_dim DH in {16, 32, 64, 128}: LPR = DH / 8 lanes per key row (8 elements each), KPW = 64 / LPR
 // keys per wave iteration
-template <typename T, int DH>
+// RAG: pos is int64[B], one position per row (mit_attention_decode_ragged); Lk stays block-uniform
+template <typename T, int DH, bool RAG = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(long H, const T* __restrict__ q, long q_batch,
                                                           const T* __restrict__ k, long k_row, long k_batch,
                                                           const T* __restrict__ v, long v_row, long v_batch,
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(long H, const T* __res
   const int bh = blockIdx.x;
   const long b = bh / H, h = bh % H;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, g = lane / LPR, c = lane % LPR;
-  const long Lk = pos ? (*pos + 1) : lk_fixed;
+  const long Lk = pos ? (pos[RAG ? b : 0] + 1) : lk_fixed;
 
   float qv[8];
   load8<T>(q + b * q_batch + h * DH + c * 8, qv);
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(long H, const T* __res
 // with U rows per wave in flight before the first use. Wave w takes keys w*U .. w*U+U-1 (+8U per
 // iteration); the 8 waves' softmax states merge once in LDS. A head's score is summed over its lanes by
 // head_sum (decode_attn.h).
-template <int DH, int U, bool NT>
+template <int DH, int U, bool NT, bool RAG = false>
 __global__ __launch_bounds__(512) void attn_decode_rows_kernel(const bf16* __restrict__ q, long q_batch,
                                                                const bf16* __restrict__ k, long k_row, long k_batch,
                                                                const bf16* __restrict__ v, long v_row, long v_batch,
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(512) void attn_decode_rows_kernel(const bf16* __res
   __shared__ float red[8][64][10];
   const long b = blockIdx.x;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const long Lk = pos ? (*pos + 1) : lk_fixed;
+  const long Lk = pos ? (pos[RAG ? b : 0] + 1) : lk_fixed;
   float qv[8];
   load8<bf16>(q + b * q_batch + lane * 8, qv);
 #pragma unroll
@@ -238,17 +239,10 @@ __global__ void embed_decode_kernel(long B, long d, const int64_t* __restrict__ 
   }
 }
 
-// one block per row: first index of the maximum (torch.argmax), NaN counts as maximal
-__global__ __launch_bounds__(256) void greedy_pick_kernel(long V, const float* __restrict__ logits, long ld,
-                                                          int64_t* __restrict__ ids, long ld_ids,
-                                                          const int64_t* pos, int64_t end_id,
-                                                          int64_t pad_id, int* __restrict__ finished,
-                                                          int* __restrict__ n_finished, int* __restrict__ ticket,
-                                                          int64_t* pos_adv) {  // may alias pos: no __restrict__
-  __shared__ float sv[4];
-  __shared__ long si[4];
-  const long b = blockIdx.x;
-  const float* row = logits + b * ld;
+// the block's row argmax (256 threads, one row): first index of the maximum (torch.argmax), NaN counts as
+// maximal; the result is thread 0's. Shared by greedy_pick_kernel and greedy_pick_ragged_kernel.
+__device__ __forceinline__ long block_row_argmax(long V, const float* __restrict__ logits, const float* __restrict__ row,
+                                                 long ld, float (&sv)[4], long (&si)[4]) {
   // (value desc, index asc), NaN largest
   auto better = [](float a, long ia, float bv, long ib) {
     const bool an = a != a, bn = bv != bv;
@@ -311,6 +305,22 @@ __global__ __launch_bounds__(256) void greedy_pick_kernel(long V, const float* _
         best = sv[k];
         bi = si[k];
       }
+  }
+  return bi;
+}
+
+// one block per row
+__global__ __launch_bounds__(256) void greedy_pick_kernel(long V, const float* __restrict__ logits, long ld,
+                                                          int64_t* __restrict__ ids, long ld_ids,
+                                                          const int64_t* pos, int64_t end_id,
+                                                          int64_t pad_id, int* __restrict__ finished,
+                                                          int* __restrict__ n_finished, int* __restrict__ ticket,
+                                                          int64_t* pos_adv) {  // may alias pos: no __restrict__
+  __shared__ float sv[4];
+  __shared__ long si[4];
+  const long b = blockIdx.x;
+  const long bi = block_row_argmax(V, logits, logits + b * ld, ld, sv, si);
+  if (threadIdx.x == 0) {
     const long p = *pos;
     if (finished[b]) {
       ids[b * ld_ids + p + 1] = pad_id;
@@ -330,6 +340,85 @@ __global__ __launch_bounds__(256) void greedy_pick_kernel(long V, const float* _
       *pos_adv = p + 1;
       *ticket = 0;
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Rolling-batch decode (mit_*_ragged): every row b at its own position row_pos[b] (int64[B]).
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void kv_store_ragged_kernel(long B, long n, const T* __restrict__ src, long s_batch, T* __restrict__ cache,
+                                       long c_row, long c_batch, const int64_t* __restrict__ row_pos) {
+  const long total = B * n;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / n, e = i % n;
+    cache[b * c_batch + row_pos[b] * c_row + e] = src[b * s_batch + e];
+  }
+}
+
+template <typename T>
+__global__ void embed_decode_ragged_kernel(long B, long d, const int64_t* __restrict__ ids, long ld_ids,
+                                           const int64_t* __restrict__ row_pos, const T* __restrict__ table,
+                                           float scale, const float* __restrict__ pe, T* __restrict__ out) {
+  const long total = B * d;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / d, e = i % d;
+    const long p = row_pos[b];
+    const int64_t id = ids[b * ld_ids + p];
+    out[i] = from_f<T>(to_f(table[id * d + e]) * scale + pe[p * d + e]);
+  }
+}
+
+// the one rule of both ragged picks, for a row that is not done: ids[b, p + 1] = pick, row_pos[b] = p + 1, done (and
+// counted once) when the pick is END or the row is full (p + 2 == limit). A row with no room (p + 1 >= limit, which a
+// caller that keeps 1 <= limit and admits no cap-1 image never has) writes nothing and is retired.
+__device__ __forceinline__ void ragged_pick_row(long b, int64_t pick, int64_t* __restrict__ ids, long ld_ids,
+                                                int64_t* __restrict__ row_pos, int64_t end_id,
+                                                const int64_t* __restrict__ limit, int* __restrict__ done,
+                                                int* __restrict__ n_done) {
+  if (done[b]) return;  // frozen: nothing of the row is written
+  const long p = row_pos[b];
+  const long lim = min((long)limit[b], ld_ids);
+  if (p + 1 < lim) {
+    ids[b * ld_ids + p + 1] = pick;
+    row_pos[b] = p + 1;
+  }
+  if (pick == end_id || p + 2 >= lim) {
+    done[b] = 1;
+    atomicAdd(n_done, 1);
+  }
+}
+
+__global__ __launch_bounds__(256) void greedy_pick_ragged_kernel(long V, const float* __restrict__ logits, long ld,
+                                                                 int64_t* __restrict__ ids, long ld_ids,
+                                                                 int64_t* __restrict__ row_pos, int64_t end_id,
+                                                                 const int64_t* __restrict__ limit,
+                                                                 int* __restrict__ done, int* __restrict__ n_done) {
+  __shared__ float sv[4];
+  __shared__ long si[4];
+  const long b = blockIdx.x;
+  if (done[b]) return;  // block-uniform: a frozen row's logits are not even read
+  const long bi = block_row_argmax(V, logits, logits + b * ld, ld, sv, si);
+  if (threadIdx.x == 0) ragged_pick_row(b, bi, ids, ld_ids, row_pos, end_id, limit, done, n_done);
+}
+
+// one block: row b's pick from the largest of its head argmax slot keys; the keys of every row, frozen ones
+// included, are reset to 0 for the next head launch
+__global__ __launch_bounds__(1024) void greedy_pick_keys_ragged_kernel(long B, unsigned long long* __restrict__ keys,
+                                                                       int64_t* __restrict__ ids, long ld_ids,
+                                                                       int64_t* __restrict__ row_pos, int64_t end_id,
+                                                                       const int64_t* __restrict__ limit,
+                                                                       int* __restrict__ done, int* __restrict__ n_done) {
+  for (long b = threadIdx.x; b < B; b += blockDim.x) {
+    unsigned long long k = 0ull;
+#pragma unroll
+    for (int sl = 0; sl < MIT_ARGMAX_SLOTS; ++sl) {
+      const unsigned long long ks = keys[sl * B + b];
+      k = ks > k ? ks : k;
+    }
+#pragma unroll
+    for (int sl = 0; sl < MIT_ARGMAX_SLOTS; ++sl) keys[sl * B + b] = 0ull;
+    ragged_pick_row(b, (int64_t)(0xFFFFFFFFu - (uint32_t)k), ids, ld_ids, row_pos, end_id, limit, done, n_done);
   }
 }
 
@@ -869,6 +958,113 @@ extern "C" int mit_greedy_pick_advance(long B, long V, const float* logits, long
   hipLaunchKernelGGL(greedy_pick_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, V, logits, ld, ids,
                      ld_ids, pos, end_id, pad_id, finished, n_finished, ticket, pos);
   MIT_LAUNCH_CHECK("mit_greedy_pick_advance");
+  return MIT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Rolling-batch entry points: the scalar-pos ones above with row_pos (int64[B]) where they take pos
+// ------------------------------------------------------------------------------------------------
+extern "C" int mit_attention_decode_ragged_plan(int dtype, long B, long H, long Dh, const void* q, long q_batch,
+                                                const void* k, long k_row, long k_batch, const void* v, long v_row,
+                                                long v_batch, const void* o, long o_batch, long Lk,
+                                                const int64_t* row_pos, const int64_t* key_tokens) {
+  // the same host decision as mit_attention_decode_plan: a position per row changes no dispatch predicate
+  return mit_attention_decode_plan(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, Lk,
+                                   row_pos, key_tokens);
+}
+
+extern "C" int mit_attention_decode_ragged(int dtype, long B, long H, long Dh, const void* q, long q_batch, const void* k,
+                                           long k_row, long k_batch, const void* v, long v_row, long v_batch, void* o,
+                                           long o_batch, long Lk, const int64_t* row_pos, const int64_t* key_tokens,
+                                           long tok_batch, int pad_idx, float scale, void* stream) {
+  MIT_RECORD([=]() { return mit_attention_decode_ragged(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, Lk, row_pos, key_tokens, tok_batch, pad_idx, scale, stream); });
+  int family = -1;
+  const int rc = plan_attn_decode(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, Lk, row_pos, &family);
+  if (rc != MIT_OK) return rc;
+  if (B <= 0 || H <= 0) return MIT_OK;
+  if (family != MIT_DECODE_ATTN_BH) {
+    const bool nt = family == MIT_DECODE_ATTN_ROWS_NT;  // row_pos == NULL: the fixed-Lk stream, as the scalar entry point
+#define MIT_ROWS_LAUNCH(DH_)                                                                                          \
+  if (nt)                                                                                                             \
+    hipLaunchKernelGGL((attn_decode_rows_kernel<DH_, 8, true, true>), dim3((unsigned)B), dim3(512), 0,                \
+                       (hipStream_t)stream, (const bf16*)q, q_batch, (const bf16*)k, k_row, k_batch, (const bf16*)v,  \
+                       v_row, v_batch, (bf16*)o, o_batch, Lk, row_pos, key_tokens, tok_batch, pad_idx, scale);        \
+  else                                                                                                                \
+    hipLaunchKernelGGL((attn_decode_rows_kernel<DH_, 8, false, true>), dim3((unsigned)B), dim3(512), 0,               \
+                       (hipStream_t)stream, (const bf16*)q, q_batch, (const bf16*)k, k_row, k_batch, (const bf16*)v,  \
+                       v_row, v_batch, (bf16*)o, o_batch, Lk, row_pos, key_tokens, tok_batch, pad_idx, scale)
+    switch (Dh) {
+      case 16: MIT_ROWS_LAUNCH(16); break;
+      case 32: MIT_ROWS_LAUNCH(32); break;
+      case 64: MIT_ROWS_LAUNCH(64); break;
+      default: MIT_ROWS_LAUNCH(128); break;
+    }
+#undef MIT_ROWS_LAUNCH
+    MIT_LAUNCH_CHECK("mit_attention_decode_ragged");
+    return MIT_OK;
+  }
+#define MIT_DECODE_LAUNCH(DH_)                                                                                         \
+  DISPATCH_DT(dtype, hipLaunchKernelGGL((attn_decode_kernel<T, DH_, true>), dim3((unsigned)(B * H)), dim3(256), 0,      \
+                                        (hipStream_t)stream, H, (const T*)q, q_batch, (const T*)k, k_row, k_batch,      \
+                                        (const T*)v, v_row, v_batch, (T*)o, o_batch, Lk, row_pos, key_tokens,          \
+                                        tok_batch, pad_idx, scale))
+  switch (Dh) {
+    case 16: MIT_DECODE_LAUNCH(16); break;
+    case 32: MIT_DECODE_LAUNCH(32); break;
+    case 64: MIT_DECODE_LAUNCH(64); break;
+    default: MIT_DECODE_LAUNCH(128); break;
+  }
+#undef MIT_DECODE_LAUNCH
+  MIT_LAUNCH_CHECK("mit_attention_decode_ragged");
+  return MIT_OK;
+}
+
+extern "C" int mit_kv_store_ragged(int dtype, long B, long n, const void* src, long s_batch, void* cache, long c_row,
+                                   long c_batch, const int64_t* row_pos, void* stream) {
+  MIT_RECORD([=]() { return mit_kv_store_ragged(dtype, B, n, src, s_batch, cache, c_row, c_batch, row_pos, stream); });
+  MIT_CHECK_ARG(src && cache && row_pos, "mit_kv_store_ragged: null pointer");
+  if (B <= 0 || n <= 0) return MIT_OK;
+  DISPATCH_DT(dtype, hipLaunchKernelGGL(kv_store_ragged_kernel<T>, dim3(grid_for(B * n)), dim3(256), 0,
+                                        (hipStream_t)stream, B, n, (const T*)src, s_batch, (T*)cache, c_row, c_batch,
+                                        row_pos));
+  MIT_LAUNCH_CHECK("mit_kv_store_ragged");
+  return MIT_OK;
+}
+
+extern "C" int mit_embed_decode_ragged(int dtype, long B, long d, const int64_t* ids, long ld_ids, const int64_t* row_pos,
+                                       const void* table, float scale, const float* pe, void* out, void* stream) {
+  MIT_RECORD([=]() { return mit_embed_decode_ragged(dtype, B, d, ids, ld_ids, row_pos, table, scale, pe, out, stream); });
+  MIT_CHECK_ARG(ids && row_pos && table && pe && out, "mit_embed_decode_ragged: null pointer");
+  if (B <= 0) return MIT_OK;
+  DISPATCH_DT(dtype, hipLaunchKernelGGL(embed_decode_ragged_kernel<T>, dim3(grid_for(B * d)), dim3(256), 0,
+                                        (hipStream_t)stream, B, d, ids, ld_ids, row_pos, (const T*)table, scale, pe,
+                                        (T*)out));
+  MIT_LAUNCH_CHECK("mit_embed_decode_ragged");
+  return MIT_OK;
+}
+
+extern "C" int mit_greedy_pick_ragged(long B, long V, const float* logits, long ld, int64_t* ids, long ld_ids,
+                                      int64_t* row_pos, int64_t end_id, const int64_t* limit, int* done, int* n_done,
+                                      void* stream) {
+  MIT_RECORD([=]() { return mit_greedy_pick_ragged(B, V, logits, ld, ids, ld_ids, row_pos, end_id, limit, done, n_done, stream); });
+  MIT_CHECK_ARG(logits && ids && row_pos && limit && done && n_done && ld >= V && V > 0 && ld_ids > 0,
+                "mit_greedy_pick_ragged: bad arguments");
+  if (B <= 0) return MIT_OK;
+  MIT_CHECK_ARG(B < (1L << 31), "mit_greedy_pick_ragged: B = %ld", B);
+  hipLaunchKernelGGL(greedy_pick_ragged_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, V, logits, ld, ids,
+                     ld_ids, row_pos, end_id, limit, done, n_done);
+  MIT_LAUNCH_CHECK("mit_greedy_pick_ragged");
+  return MIT_OK;
+}
+
+extern "C" int mit_greedy_pick_keys_ragged(long B, unsigned long long* keys, int64_t* ids, long ld_ids, int64_t* row_pos,
+                                           int64_t end_id, const int64_t* limit, int* done, int* n_done, void* stream) {
+  MIT_RECORD([=]() { return mit_greedy_pick_keys_ragged(B, keys, ids, ld_ids, row_pos, end_id, limit, done, n_done, stream); });
+  MIT_CHECK_ARG(keys && ids && row_pos && limit && done && n_done && ld_ids > 0, "mit_greedy_pick_keys_ragged: bad arguments");
+  MIT_CHECK_ARG(B > 0 && B < (1L << 30), "mit_greedy_pick_keys_ragged: B = %ld", B);
+  hipLaunchKernelGGL(greedy_pick_keys_ragged_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, B, keys, ids, ld_ids,
+                     row_pos, end_id, limit, done, n_done);
+  MIT_LAUNCH_CHECK("mit_greedy_pick_keys_ragged");
   return MIT_OK;
 }
 

@@ -380,20 +380,24 @@ class DecodeState:
     cons: Optional[DecodeConstraints] = None  # active constraints (TransformerDecoder._constrain_begin), else None
     suppress: Optional[torch.Tensor] = None   # with cons: the suppressed ids on the device (int64), or None
     forced: Optional[torch.Tensor] = None     # with cons: int64 [rows, Lp + 1], column j + 1 = prompt token j, -1 = free
+    row_pos: Optional[torch.Tensor] = None    # RollingState: int64 [rows], one position per row (then pos is None)
 
     def __init__(self, dec: "TransformerDecoder", B: int, S: int, max_len: int, start_id: int, end_id: int,
-                 images: Optional[int] = None, kv_dtype: Optional[str] = None):
+                 images: Optional[int] = None, kv_dtype: Optional[str] = None, shared_pos: bool = True):
         """B rows; images: how many memories the cross-attention K/V holds (default: one per row); kv_dtype:
-        resolve_kv_dtype."""
+        resolve_kv_dtype; shared_pos = False (RollingState): no pos / finished / n_finished are allocated, the
+        subclass holds a position per row instead."""
         dev, dt = dec.device, dec.dtype
         d, F, L, V = dec.d, dec.F, dec.L, dec.V
         self.kv_dtype = resolve_kv_dtype(kv_dtype, dt)
         self.B, self.S, self.max_len, self.end_id = B, S, max_len, int(end_id)
         self.ids = torch.full((B, max_len), dec.pad_idx, dtype=torch.int64, device=dev)
         self.ids[:, 0] = int(start_id)
-        self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.finished = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.n_finished = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.pos = self.finished = self.n_finished = None
+        if shared_pos:
+            self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.finished = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.n_finished = torch.zeros(1, dtype=torch.int32, device=dev)
         # per layer contiguous [L][B*S][2d] (K | V): a decode attention block (b, h) then reads its S keys
         # at a 2 KiB stride instead of the training layout's L * 2d row (12 KiB at cfg1), which left the
         # S = 197 cross attention at ~2.6 TB/s on DRAM page misses
@@ -484,6 +488,85 @@ class SampleState(DecodeState):
         self.seed = torch.tensor([s - (1 << 64) if s >= (1 << 63) else s], dtype=torch.int64, device=dev)
         if not hasattr(self, "ticket"):  # the fused state has one already
             self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+class _PoolView:
+    """The cross-attention K/V tensors of `n` pool images from pool index `at`, under the names _cross_kv_begin
+    writes through (kv / kv8 / kv_scale of a DecodeState)."""
+
+    def __init__(self, stt: "RollingState", at: int, n: int):
+        S = stt.S
+        self.kv = stt.pool_kv[:, at * S:(at + n) * S] if stt.pool_kv is not None else None
+        self.kv8 = stt.pool_kv8[:, at * S:(at + n) * S] if stt.pool_kv8 is not None else None
+        self.kv_scale = stt.pool_scale[:, at:at + n] if stt.pool_scale is not None else None
+
+
+class RollingState(DecodeState):
+    """Device state of a rolling-batch greedy decode (TransformerDecoder.rolling_begin / rolling_fill / rolling_admit
+    / rolling_step): a DecodeState of `slots` rows in which every row has its OWN position. In place of pos /
+    finished / n_finished it holds row_pos (int64 [slots]), done (int32 [slots]), n_done (int32 [1]) -- three views
+    of one buffer `poll_dev`, so that a poll is one device-to-host copy -- and limit (int64 [slots], the ids a row
+    may hold). A pool of `pool` images' cross-attention K/V (pool_kv, or pool_kv8 + pool_scale with kv_dtype "fp8")
+    feeds the slots: mit_slot_admit copies an image's rows into a slot and resets the slot. Every slot starts EMPTY:
+    done = 1, n_done = slots, K/V (and scales) zero, ids[:, 0] = START, so stepping an empty slot is finite
+    arithmetic whose results nobody reads."""
+
+    def __init__(self, dec: "TransformerDecoder", slots: int, S: int, max_len: int, start_id: int, end_id: int,
+                 pool: Optional[int] = None, kv_dtype: Optional[str] = None):
+        # no shared position: pos / finished / n_finished stay None, so no scalar-pos launch can be given one
+        super().__init__(dec, slots, S, max_len, start_id, end_id, kv_dtype=kv_dtype, shared_pos=False)
+        dev = dec.device
+        self.slots, self.pool, self.start_id = slots, slots if pool is None else int(pool), int(start_id)
+        # [row_pos: 8 * slots | done: 4 * slots | n_done: 4 | pad] bytes
+        nb = 12 * slots + 8
+        self.poll_dev = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        self.row_pos = self.poll_dev[:8 * slots].view(torch.int64)
+        self.done = self.poll_dev[8 * slots:12 * slots].view(torch.int32)
+        self.n_done = self.poll_dev[12 * slots:12 * slots + 4].view(torch.int32)
+        self.done.fill_(1)
+        self.n_done.fill_(slots)
+        self.poll_host = torch.zeros(nb, dtype=torch.uint8).pin_memory() if dev.type == "cuda" else \
+            torch.zeros(nb, dtype=torch.uint8)
+        self.limit = torch.ones(slots, dtype=torch.int64, device=dev)
+        for c in self.cache:  # row 0 of an empty slot is read by the first steps before anything was admitted
+            c.zero_()
+        L, d = dec.L, dec.d
+        if self.kv8 is not None:
+            self.kv8.zero_()
+            self.kv_scale.zero_()
+            self.pool_kv, self.pool_kv8 = None, torch.empty(L, self.pool * S, 2 * d, dtype=torch.uint8, device=dev)
+            self.pool_scale = torch.empty(L, self.pool, 2 * dec.H, dtype=torch.float32, device=dev)
+        else:
+            self.kv.zero_()
+            self.pool_kv8, self.pool_scale = None, None
+            self.pool_kv = torch.empty(L, self.pool * S, 2 * d, dtype=dec.dtype, device=dev)
+        self.triples = torch.zeros(slots, 3, dtype=torch.int64, device=dev)
+        self.triples_host = torch.zeros(slots, 3, dtype=torch.int64)
+        self.triples_ev = None
+        self.rows_idx = torch.zeros(slots, dtype=torch.int64, device=dev)       # slots whose ids a harvest takes
+        self.rows_dev = torch.empty(slots, max_len, dtype=torch.int64, device=dev)
+        self.rows_host = torch.empty(slots, max_len, dtype=torch.int64)
+        if dev.type == "cuda":
+            self.rows_host = self.rows_host.pin_memory()
+        if dev.type == "cuda":
+            self.triples_host = self.triples_host.pin_memory()
+
+    def harvest(self, slot_list):
+        """The ids rows of the given slots, [len(slot_list), max_len] on the host (pinned): only those rows are
+        gathered and copied, stream-ordered, and waited for -- before the admit launch that reuses the slots."""
+        n = len(slot_list)
+        self.rows_idx[:n].copy_(torch.tensor(slot_list, dtype=torch.int64), non_blocking=True)
+        torch.index_select(self.ids, 0, self.rows_idx[:n], out=self.rows_dev[:n])
+        self.rows_host[:n].copy_(self.rows_dev[:n], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return self.rows_host[:n]
+
+    def snapshot(self):
+        """(done flags, row_pos) of every slot as Python lists: one stream-ordered copy, then a wait for it."""
+        self.poll_host.copy_(self.poll_dev, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        n = self.slots
+        return (self.poll_host[8 * n:12 * n].view(torch.int32).tolist(), self.poll_host[:8 * n].view(torch.int64).tolist())
 
 
 class TransformerDecoder:
@@ -1064,11 +1147,23 @@ class TransformerDecoder:
                                V=self.V)
             native.step_inc(stt.pos)
 
+    def _embed_step(self, stt: "DecodeState"):
+        """stt.x = the embedding of every row's current token plus its position's encoding."""
+        table = self.store.w("token_embedding.weight")
+        if stt.row_pos is not None:
+            native.embed_decode_ragged(stt.ids, stt.row_pos, table, math.sqrt(self.d), self.pe, stt.x)
+        else:
+            native.embed_decode(stt.ids, stt.pos, table, math.sqrt(self.d), self.pe, stt.x)
+
     def _attn_self(self, stt: "DecodeState", cache: torch.Tensor, scale: float):
         """The step's causal self-attention over the cache (query: stt.qkv's first d columns) -> stt.o; a beam
         state reads each key from its ancestor's row."""
         d, Tm = self.d, stt.max_len
-        if stt.K:
+        if stt.row_pos is not None:
+            native.attention_decode_ragged(stt.qkv, 3 * d, cache, 2 * d, Tm * 2 * d, cache[:, :, d:], 2 * d, Tm * 2 * d,
+                                           stt.o, d, stt.B, self.H, row_pos=stt.row_pos, key_tokens=stt.ids,
+                                           tok_batch=Tm, pad_idx=self.pad_idx, scale=scale, Dh=self.hd)
+        elif stt.K:
             native.attention_decode_beam(stt.qkv, 3 * d, cache, 2 * d, Tm * 2 * d, cache[:, :, d:], 2 * d, Tm * 2 * d,
                                          stt.o, d, stt.B, self.H, pos=stt.pos, group=stt.K, anc=stt.anc,
                                          key_tokens=stt.ids, tok_batch=Tm, pad_idx=self.pad_idx, scale=scale,
@@ -1100,13 +1195,16 @@ class TransformerDecoder:
         d, L = self.d, self.L
         st, w = self.store, self.store.w
         B, Tm = stt.B, stt.max_len
-        native.embed_decode(stt.ids, stt.pos, w("token_embedding.weight"), math.sqrt(d), self.pe, stt.x)
+        self._embed_step(stt)
         x = stt.x
         for l in range(L):
             pre = f"layers.{l}."
             cache = stt.cache[l]
             native.linear(x, w(pre + "self_in.weight"), stt.qkv, bias=st.p(pre + "self_in.bias"))
-            native.kv_store(stt.qkv[:, d:], 3 * d, cache, 2 * d, Tm * 2 * d, B, 2 * d, stt.pos)
+            if stt.row_pos is not None:
+                native.kv_store_ragged(stt.qkv[:, d:], 3 * d, cache, 2 * d, Tm * 2 * d, B, 2 * d, stt.row_pos)
+            else:
+                native.kv_store(stt.qkv[:, d:], 3 * d, cache, 2 * d, Tm * 2 * d, B, 2 * d, stt.pos)
             self._attn_self(stt, cache, 1.0 / math.sqrt(self.hd))
             native.linear(stt.o, w(pre + "self_out.weight"), stt.y, bias=st.p(pre + "self_out.bias"))
             native.layernorm_fwd(x, st.p(pre + "norm1.weight"), st.p(pre + "norm1.bias"), 1e-5, stt.x1, r=stt.y)
@@ -1143,7 +1241,7 @@ class TransformerDecoder:
         z1, z2, z3 = stt.z
         s1, s2, s3 = stt.zst
         scale = 1.0 / math.sqrt(self.hd)
-        native.embed_decode(stt.ids, stt.pos, w("token_embedding.weight"), math.sqrt(d), self.pe, stt.x)
+        self._embed_step(stt)
         for l in range(L):
             pre = f"layers.{l}."
             cache = stt.cache[l]
@@ -1154,8 +1252,14 @@ class TransformerDecoder:
                 a, a_ln = z3, (s3, p(q3 + "weight"), p(q3 + "bias"))
             ln1 = (s1, p(pre + "norm1.weight"), p(pre + "norm1.bias"))
             ln2 = (s2, p(pre + "norm2.weight"), p(pre + "norm2.bias"))
-            native.decode_gemm(a, w(pre + "self_in.weight"), out=stt.qkv, bias=p(pre + "self_in.bias"), a_ln=a_ln,
-                               cache=cache, c_row=2 * d, c_batch=Tm * 2 * d, kv_col0=d, pos=stt.pos)
+            if stt.row_pos is not None:
+                # per-row cache rows: the in_proj without its cache epilogue, then the K|V columns of stt.qkv (the
+                # same bf16 values the epilogue would have stored) to cache row row_pos[b] of each row
+                native.decode_gemm(a, w(pre + "self_in.weight"), out=stt.qkv, bias=p(pre + "self_in.bias"), a_ln=a_ln)
+                native.kv_store_ragged(stt.qkv[:, d:], 3 * d, cache, 2 * d, Tm * 2 * d, stt.B, 2 * d, stt.row_pos)
+            else:
+                native.decode_gemm(a, w(pre + "self_in.weight"), out=stt.qkv, bias=p(pre + "self_in.bias"), a_ln=a_ln,
+                                   cache=cache, c_row=2 * d, c_batch=Tm * 2 * d, kv_col0=d, pos=stt.pos)
             self._attn_self(stt, cache, scale)
             native.decode_gemm(stt.o, w(pre + "self_out.weight"), bias=p(pre + "self_out.bias"), residual=a, r_ln=a_ln,
                                z_out=z1, stats_out=s1)
@@ -1170,6 +1274,72 @@ class TransformerDecoder:
         q3 = f"layers.{L - 1}.norm3."
         native.decode_layernorm(z3, s3, p(q3 + "weight"), p(q3 + "bias"), stt.x)
         return stt.x
+
+    # --- rolling-batch greedy decode: one position per row, slots refilled (csrc/rolling.hip) -----------
+    def rolling_begin(self, S: int, slots: int, max_len: int, start_id: int, end_id: int, pool: Optional[int] = None,
+                      kv_dtype: Optional[str] = None) -> "RollingState":
+        """Allocate a rolling decode of `slots` rows over memories of S rows and a K/V pool of `pool` images (default
+        `slots`). Every slot starts empty (RollingState); rolling_fill puts images into the pool, rolling_admit hands
+        pool images to slots, rolling_step advances every slot that is not done by one token."""
+        if max_len > self.pe.shape[0]:
+            raise ValueError(f"max_len {max_len} exceeds the positional table ({self.pe.shape[0]} = "
+                             f"decoder_max_seq_len; the reference's PositionalEncoding would fail too)")
+        if slots < 1 or (pool is not None and pool < 1):
+            raise ValueError(f"rolling decode needs slots >= 1 and pool >= 1 (got {slots}, {pool})")
+        if max_len < 2:
+            raise ValueError("rolling decode needs max_len >= 2 (a cap of 1 takes no slot)")
+        return RollingState(self, slots, S, max_len, start_id, end_id, pool=pool, kv_dtype=kv_dtype)
+
+    def rolling_fill(self, stt: "RollingState", mem: torch.Tensor, mem_ld: int, S: int, n: int, at: int = 0):
+        """The cross-attention K/V of the n freshly encoded images of mem [n*S, d] (row stride mem_ld) into pool
+        entries at .. at+n-1: _cross_kv_begin's GEMMs (and FP8 quantisation, whose scales are per (layer, image,
+        head) and so do not depend on the other images of the chunk)."""
+        if S != stt.S or n < 0 or at < 0 or at + n > stt.pool:
+            raise ValueError(f"rolling_fill: {n} images of {S} rows at pool entry {at} do not fit a pool of {stt.pool} "
+                             f"images of {stt.S} rows")
+        if n:
+            self._cross_kv_begin(_PoolView(stt, at, n), mem, mem_ld, S, n)
+
+    def rolling_admit(self, stt: "RollingState", triples):
+        """One mit_slot_admit launch for the (slot, pool entry, cap) triples: each slot gets the entry's K/V, START,
+        position 0, done = 0 and limit = cap (2 <= cap <= max_len). The host must have taken a slot's ids before it
+        is named here. No triples: no launch."""
+        m = len(triples)
+        if m == 0:
+            return
+        for s_, e_, c_ in triples:
+            if not (0 <= s_ < stt.slots and 0 <= e_ < stt.pool and 2 <= c_ <= stt.max_len):
+                raise ValueError(f"rolling_admit: bad triple (slot {s_}, pool entry {e_}, cap {c_})")
+        if len({t[0] for t in triples}) != m:
+            raise ValueError("rolling_admit: a slot is named twice")
+        if stt.triples_ev is not None:  # the previous admission's copy out of the pinned triples has run
+            stt.triples_ev.synchronize()
+        stt.triples_host[:m] = torch.tensor(triples, dtype=torch.int64)
+        stt.triples[:m].copy_(stt.triples_host[:m], non_blocking=True)
+        if stt.triples_host.is_pinned():
+            stt.triples_ev = torch.cuda.Event()
+            stt.triples_ev.record()
+        fp8 = stt.kv8 is not None
+        native.slot_admit(stt.triples, m, stt.pool_kv8 if fp8 else stt.pool_kv, stt.kv8 if fp8 else stt.kv, stt.S,
+                          stt.pool_scale, stt.kv_scale, stt.ids, stt.start_id, stt.row_pos, stt.done, stt.limit,
+                          stt.n_done)
+
+    def rolling_step(self, stt: "RollingState"):
+        """One greedy token for every slot that is not done, each at its own position row_pos[b] -> ids[b, p + 1];
+        a done (or empty) slot is frozen. The launch list does not depend on the state (admission is a separate
+        launch), so one recording replays for every step. The fused bf16 step keeps the head's argmax epilogue."""
+        if stt.fused:
+            x = self._step_body_fused(stt)
+            w, p, V = self.store.w, self.store.p, self.V
+            native.gemm(x, w("fc_out.weight")[:V], None, stt.B, V, self.d, bias=p("fc_out.bias")[:V],
+                        argmax_keys=stt.keys)
+            native.greedy_pick_keys_ragged(stt.keys, stt.ids, stt.row_pos, stt.end_id, stt.limit, stt.done, stt.n_done)
+            return
+        x = self._step_body(stt)
+        st, w = self.store, self.store.w
+        native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
+        native.greedy_pick_ragged(stt.logits, stt.ids, stt.row_pos, stt.end_id, stt.limit, stt.done, stt.n_done,
+                                  V=self.V)
 
     # --- beam search on the same step (csrc/beam.hip) ---------------------------------------------------
     def beam_begin(self, mem: torch.Tensor, mem_ld: int, S: int, B: int, K: int, max_len: int, start_id: int,

@@ -64,7 +64,8 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
                       max_len: int = config.MAX_SEQ_LEN, batch_size: int = 256, beam_size: Optional[int] = None,
                       length_penalty: float = 0.0, temperature: Optional[float] = None, top_k: int = 0,
                       top_p: float = 1.0, seed: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
-                      min_length: int = 0, suppress_tokens=(), prompts=None, kv_dtype: Optional[str] = None):
+                      min_length: int = 0, suppress_tokens=(), prompts=None, kv_dtype: Optional[str] = None,
+                      rolling_slots: Optional[int] = None):
     """Captions for a list of PIL images / HWC arrays or a [B,3,H,W] pixel tensor, `batch_size` images
     per batched decode. Returns [(processed ids, text)] — text is None without a `decode` function
     (the BPE tokenizer, tokenizer.py, is a host-side library outside this path).
@@ -78,7 +79,29 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
     prompts is one token list for every image or one list per image of `images`; a prompt's tokens are part of the
     processed ids and so of the text.
     kv_dtype: "bf16" or "fp8", how the decode holds the cross-attention K/V (generate_batch); passed on only when
-    given, as the constraints are."""
+    given, as the constraints are.
+    rolling_slots: a number decodes greedily with rolling batching (generate_rolling_iter: that many decode slots,
+    a finished caption's slot handed to the next image; `batch_size` images per encoder chunk): the same
+    (ids, text) list, sooner when the captions' lengths differ. It excludes beam_size, temperature and every decode
+    constraint."""
+    if rolling_slots is not None:
+        if beam_size is not None or temperature is not None or repetition_penalty != 1.0 or no_repeat_ngram_size \
+                or min_length or suppress_tokens or prompts:
+            raise ValueError("generate_captions: rolling_slots is the greedy decode; it excludes beam_size, "
+                             "temperature and the decode constraints")
+        if isinstance(images, torch.Tensor):
+            pv = images if images.dim() == 4 else images.unsqueeze(0)
+        else:
+            pv = model.image_processor(images=list(images), return_tensors="pt")["pixel_values"]
+        kw = {} if kv_dtype is None else {"kv_dtype": kv_dtype}
+        got = dict(model.generate_rolling_iter((pv[i:i + batch_size] for i in range(0, pv.shape[0], batch_size)),
+                                               start_token_id, end_token_id, max_len=max_len, slots=rolling_slots,
+                                               encode_batch=batch_size, **kw))
+        out = []
+        for i in range(pv.shape[0]):
+            p = postprocess_ids(got[i], start_token_id, end_token_id)
+            out.append((p, clean_text(decode(p)) if decode is not None else None))
+        return out
     cons = {}
     if kv_dtype is not None:
         cons["kv_dtype"] = kv_dtype
@@ -204,6 +227,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--kv_dtype", choices=["bf16", "fp8"], default=None,
                     help="storage of the cross-attention K/V: fp8 halves its memory and the bytes a token step streams "
                          "(bf16 checkpoints; default: env MIT_DECODE_KV, else bf16)")
+    ap.add_argument("--rolling_slots", type=int, default=None,
+                    help="greedy decode with rolling batching on this many slots: a finished caption's slot goes to "
+                         "the next image (excludes --beam_size, --temperature and the constraints)")
     ap.add_argument("--score_file", default=None,
                     help="score instead of generating: a JSON file holding one list of candidate id lists (scored "
                          "against every image) or one such list per image; prints each image's ranking")
@@ -236,6 +262,8 @@ def decode_options(args) -> dict:
         o["prompts"] = list(args.prompt_ids)
     if args.kv_dtype is not None:
         o["kv_dtype"] = args.kv_dtype
+    if args.rolling_slots is not None:
+        o["rolling_slots"] = args.rolling_slots
     return o
 
 

@@ -27,7 +27,9 @@ import torch
 import config
 import data
 import native
-from decoder import DecodeConstraints, TransformerDecoder, decoder_entries, flat_to_reference, reference_to_flat
+import rolling
+from decoder import (DecodeConstraints, TransformerDecoder, decoder_entries, flat_to_reference, reference_to_flat,
+                     resolve_kv_dtype)
 from encoder import VisionEncoder, build_encoder
 from params import FlatParams
 
@@ -702,6 +704,127 @@ class ImageToTextModel:
         for stt in states:
             out.extend(stt.token_lists())
         return out
+
+    # --- rolling-batch greedy captioning (decoder.RollingState, rolling.RollingScheduler) -----------------
+    def generate_rolling_iter(self, batches, start_token_id: int, end_token_id: int, max_len: int = 100,
+                              slots: int = 256, check_every: Optional[int] = None, max_lens=None,
+                              kv_dtype: Optional[str] = None, use_graph: bool = True,
+                              encode_batch: Optional[int] = None, pool: Optional[int] = None,
+                              streams: Optional[int] = None, repetition_penalty: float = 1.0,
+                              no_repeat_ngram_size: int = 0, min_length: int = 0, suppress_tokens=(), prompts=None):
+        """Greedy captions of a stream of images with in-flight ("rolling") batching: `slots` decode rows are kept,
+        every row at its own position; when a row's caption ends (END, or its cap) its slot is handed to the next
+        image while the other rows go on, so a dataset costs about mean(length) token steps per `slots` images where
+        generate_batch pays max(length). Yields (image index, ids) in COMPLETION order; the ids are exactly what
+        generate_batch returns for that image (rows never interact in greedy decoding and every kernel computes a
+        row the same way whatever its neighbours and positions are).
+
+        batches: an iterable of pixel tensors [n_i, 3, H, W] (or one tensor); images are numbered in arrival order
+        and encoded `encode_batch` at a time (default `slots`) into a K/V pool of `pool` images (default: one
+        chunk; a multiple of encode_batch). max_lens: an optional per-image cap, 1 <= cap <= max_len, indexed by
+        image number (a cap of 1 yields [START] and takes no slot). check_every: token steps between two polls of
+        the device's done flags (default rolling.CHECK_EVERY_DEFAULT). kv_dtype: as generate_batch. use_graph /
+        env MIT_DECODE_LAUNCH: the step is recorded once and replayed as a launch plan ("plan"; "graph" means the
+        same here: the recorded plan is what replays between admissions), or issued eagerly ("eager",
+        use_graph=False).
+
+        Raises ValueError, before any launch, for decode constraints or prompts (the constraint kernel reads one
+        shared position), streams > 1, slots < 1, caps outside [1, max_len] and max_len past the positional
+        table."""
+        dec = self.decoder
+        if DecodeConstraints(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts).active():
+            raise ValueError("rolling decode does not take decode constraints or prompts (use generate_batch)")
+        if streams is not None and int(streams) > 1:
+            raise ValueError("rolling decode runs one row group (streams > 1 is generate_batch's)")
+        if int(slots) < 1:
+            raise ValueError(f"rolling decode needs slots >= 1 (got {slots})")
+        if max_len < 1 or max_len > dec.pe.shape[0]:
+            raise ValueError(f"max_len {max_len} must be in 1..{dec.pe.shape[0]} (the positional table, "
+                             f"decoder_max_seq_len)")
+        if max_lens is not None:
+            max_lens = [int(c) for c in max_lens]
+            bad = [(i, c) for i, c in enumerate(max_lens) if not 1 <= c <= max_len]
+            if bad:
+                raise ValueError(f"max_lens must lie in 1..{max_len}: image {bad[0][0]} has {bad[0][1]}")
+        resolve_kv_dtype(kv_dtype, self.dtype)
+        sch = rolling.RollingScheduler(int(slots), check_every, encode_batch, pool)
+        self.last_rolling_schedule = sch  # its counters (steps, polls, admits, chunks) once the iterator is spent
+        return self._rolling_run(sch, batches, int(start_token_id), int(end_token_id), int(max_len), max_lens, kv_dtype,
+                                 use_graph)
+
+    def generate_rolling(self, batches, start_token_id: int, end_token_id: int, max_len: int = 100, **kwargs):
+        """generate_rolling_iter collected: the token lists in input order (what generate_batch returns for the
+        concatenated images)."""
+        got = dict(self.generate_rolling_iter(batches, start_token_id, end_token_id, max_len, **kwargs))
+        return [got[i] for i in range(len(got))]
+
+    @staticmethod
+    def _rolling_chunks(batches, n: int):
+        """The images of an iterable of pixel tensors (or one tensor) regrouped into tensors of exactly n images (the
+        last one smaller)."""
+        if isinstance(batches, torch.Tensor):
+            batches = [batches]
+        held, have = [], 0
+        for b in batches:
+            if b.dim() == 3:
+                b = b.unsqueeze(0)
+            while b.shape[0]:
+                take = min(n - have, b.shape[0])
+                held.append(b[:take])
+                have += take
+                b = b[take:]
+                if have == n:
+                    yield held[0] if len(held) == 1 else torch.cat([h.to(held[0].device) for h in held])
+                    held, have = [], 0
+        if have:
+            yield held[0] if len(held) == 1 else torch.cat([h.to(held[0].device) for h in held])
+
+    @torch.no_grad()
+    def _rolling_run(self, sch, batches, start_id, end_id, max_len, max_lens, kv_dtype, use_graph):
+        self.eval()
+        dec = self.decoder
+        source = self._rolling_chunks(batches, sch.encode_batch)
+        stt, run = None, None
+        launch = os.environ.get("MIT_DECODE_LAUNCH", "plan") if use_graph else "eager"
+        while True:
+            while True:  # chunks and admissions until no free slot is left that the source could fill
+                while sch.wants_chunk():
+                    pv = next(source, None)
+                    if pv is None:
+                        sch.close()
+                        break
+                    n, i0 = pv.shape[0], sch.next_image
+                    if max_lens is not None and i0 + n > len(max_lens):
+                        raise ValueError(f"max_lens holds {len(max_lens)} caps, the source at least {i0 + n} images")
+                    caps = max_lens[i0:i0 + n] if max_lens is not None else [max_len] * n
+                    at, trivial = sch.add_chunk(caps)
+                    if len(trivial) < n:  # some image of the chunk needs a slot: encode it, K/V into the pool
+                        mem, mem_ld, S, _, _ = self._encode_memory(pv.to(self.device).float())
+                        if stt is None:
+                            stt = dec.rolling_begin(S, sch.slots, max(max_len, 2), start_id, end_id, pool=sch.pool,
+                                                    kv_dtype=kv_dtype)
+                            dec.rolling_step(stt)  # every slot is empty: warms every kernel, moves nothing
+                            if launch in ("plan", "graph"):
+                                run = native.record(lambda: dec.rolling_step(stt)).run
+                            else:
+                                run = lambda: dec.rolling_step(stt)  # noqa: E731
+                        dec.rolling_fill(stt, mem, mem_ld, S, n, at)
+                    for i in trivial:
+                        yield i, [start_id]
+                triples = sch.admissions()
+                if triples:  # launched before the next chunk may overwrite the pool region it reads
+                    dec.rolling_admit(stt, triples)
+                if not (triples and sch.wants_chunk()):
+                    break
+            if sch.finished():
+                return
+            for _ in range(sch.next_steps()):
+                run()
+            harvest = sch.poll(*stt.snapshot())
+            if harvest:
+                rows = stt.harvest([h[0] for h in harvest])  # the newly done rows only, before their slots are reused
+                for r, (_, image, n_ids) in enumerate(harvest):
+                    yield image, rows[r, :n_ids].tolist()
 
     @torch.no_grad()
     def generate_beam_batch(self, images, start_token_id: int, end_token_id: int, max_len: int = 100,

@@ -193,6 +193,13 @@ SIGNATURES = {
     "mit_kv_quantize_fp8": (I, [L, L, L, L, vp, L, L, vp, L, L, vp, vp]),
     "mit_attention_decode_fp8": (I, [L, L, L, vp, L, vp, L, L, vp, L, L, vp, vp, L, vp, L, L, L, Fl, vp]),
     "mit_attention_decode_fp8_plan": (I, [L, L, L, vp, L, vp, L, L, vp, L, L, vp, vp, L, vp, L, L, L]),
+    "mit_attention_decode_ragged": (I, [I, L, L, L, vp, L, vp, L, L, vp, L, L, vp, L, L, vp, vp, L, I, Fl, vp]),
+    "mit_attention_decode_ragged_plan": (I, [I, L, L, L, vp, L, vp, L, L, vp, L, L, vp, L, L, vp, vp]),
+    "mit_kv_store_ragged": (I, [I, L, L, vp, L, vp, L, L, vp, vp]),
+    "mit_embed_decode_ragged": (I, [I, L, L, vp, L, vp, vp, Fl, vp, vp, vp]),
+    "mit_greedy_pick_ragged": (I, [L, L, vp, L, vp, L, vp, ctypes.c_int64, vp, vp, vp, vp]),
+    "mit_greedy_pick_keys_ragged": (I, [L, vp, vp, L, vp, ctypes.c_int64, vp, vp, vp, vp]),
+    "mit_slot_admit": (I, [L, vp, L, L, L, vp, L, vp, L, vp, vp, L, vp, L, ctypes.c_int64, vp, vp, vp, vp, vp]),
 }
 
 
@@ -951,6 +958,62 @@ def attention_decode_fp8_plan(R, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row,
     -1 for rejected arguments. Pointers are integers (addresses) or None."""
     return lib().mit_attention_decode_fp8_plan(R, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, k_scale,
                                                v_scale, scale_batch, o, o_batch, Lk, group)
+
+
+# --- rolling-batch decoding: one position per row (decode.hip, rolling.hip) --------------------------
+def attention_decode_ragged(q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, B, H, *, Lk=0, row_pos=None,
+                            key_tokens=None, tok_batch=0, pad_idx=0, scale=0.125, Dh=64):
+    """attention_decode with Lk = row_pos[b] + 1 for row b (row_pos: int64 [B] on the device)."""
+    _check(lib().mit_attention_decode_ragged(dtype_code(q), B, H, Dh, ptr(q), q_batch, ptr(k), k_row, k_batch, ptr(v),
+                                             v_row, v_batch, ptr(o), o_batch, Lk, ptr(row_pos), ptr(key_tokens),
+                                             tok_batch, pad_idx, scale, stream_ptr()), "mit_attention_decode_ragged")
+
+
+def attention_decode_ragged_plan(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o, o_batch, *, Lk=0,
+                                 row_pos=None, key_tokens=None) -> int:
+    """The family attention_decode_ragged would launch: attention_decode_plan's for the same arguments (host only)."""
+    return lib().mit_attention_decode_ragged_plan(dtype, B, H, Dh, q, q_batch, k, k_row, k_batch, v, v_row, v_batch, o,
+                                                  o_batch, Lk, row_pos, key_tokens)
+
+
+def kv_store_ragged(src, s_batch, cache, c_row, c_batch, B, n, row_pos):
+    _check(lib().mit_kv_store_ragged(dtype_code(src), B, n, ptr(src), s_batch, ptr(cache), c_row, c_batch, ptr(row_pos),
+                                     stream_ptr()), "mit_kv_store_ragged")
+
+
+def embed_decode_ragged(ids, row_pos, table, scale, pe, out):
+    B, ld = ids.shape
+    _check(lib().mit_embed_decode_ragged(dtype_code(table), B, table.shape[1], ptr(ids), ld, ptr(row_pos), ptr(table),
+                                         scale, ptr(pe), ptr(out), stream_ptr()), "mit_embed_decode_ragged")
+
+
+def greedy_pick_ragged(logits, ids, row_pos, end_id, limit, done, n_done, V=None):
+    """Rows that are not done: ids[b, row_pos[b] + 1] = argmax, row_pos[b] += 1, done on END or at limit[b] ids."""
+    B = logits.shape[0]
+    V = V if V is not None else logits.shape[1]
+    _check(lib().mit_greedy_pick_ragged(B, V, ptr(logits), logits.stride(0), ptr(ids), ids.shape[1], ptr(row_pos),
+                                        int(end_id), ptr(limit), ptr(done), ptr(n_done), stream_ptr()),
+           "mit_greedy_pick_ragged")
+
+
+def greedy_pick_keys_ragged(keys, ids, row_pos, end_id, limit, done, n_done):
+    """greedy_pick_ragged from the argmax keys a head GEMM (argmax_keys=keys) left; the keys are reset to 0."""
+    B = ids.shape[0]
+    if keys.numel() != ARGMAX_SLOTS * B:
+        raise NativeError(f"greedy_pick_keys_ragged: keys must hold {ARGMAX_SLOTS} x B = {ARGMAX_SLOTS * B} entries")
+    _check(lib().mit_greedy_pick_keys_ragged(B, ptr(keys), ptr(ids), ids.shape[1], ptr(row_pos), int(end_id), ptr(limit),
+                                             ptr(done), ptr(n_done), stream_ptr()), "mit_greedy_pick_keys_ragged")
+
+
+def slot_admit(triples, m, pool_kv, kv, S, pool_scale, scale, ids, start_id, row_pos, done, limit, n_done):
+    """m admissions (mit_slot_admit): triples int64 [>= m, 3] on the device, (slot, pool image, cap); pool_kv
+    [L, pool*S, 2d] -> kv [L, slots*S, 2d] (any dtype: bytes), with scales [L, images, n] when given."""
+    L = kv.shape[0]
+    row_bytes = kv.shape[2] * kv.element_size()
+    _check(lib().mit_slot_admit(m, ptr(triples), L, S, row_bytes, ptr(pool_kv), pool_kv.shape[1] // S, ptr(kv),
+                                kv.shape[1] // S, ptr(pool_scale), ptr(scale),
+                                scale.shape[2] if scale is not None else 0, ptr(ids), ids.shape[1], int(start_id),
+                                ptr(row_pos), ptr(done), ptr(limit), ptr(n_done), stream_ptr()), "mit_slot_admit")
 
 
 # --- beam-search decoding (beam.hip) ---------------------------------------------------------------
