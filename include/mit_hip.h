@@ -522,6 +522,48 @@ int mit_slot_admit(long m, const int64_t* triples, long L, long S, long row_byte
                    void* kv, long slots, const float* pool_scale, float* scale, long n_scale, int64_t* ids, long ld_ids,
                    int64_t start_id, int64_t* row_pos, int* done, int64_t* limit, int* n_done, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Rolling-batch decode, sampled and constrained (csrc/constrain.hip, csrc/sample.hip, csrc/rolling.hip): the
+ * constraint launch and the sampled pick with one position PER ROW, and the admission that resets what they
+ * read. Asynchronous on `stream`, recordable (every argument check runs before the call is recorded or anything
+ * is launched), deterministic: one 256-thread block per row, block-uniform position, no float atomics, a second
+ * launch on the same inputs is bitwise equal. row_pos is trusted as above.
+ * logits_constrain_ragged: mit_logits_constrain (same edits, same order, same argument checks) with p = row_pos[r]
+ *   for row r, no ancestor table and group 1. done (int32 [R], may be NULL) replaces finished: a row with
+ *   done[r] != 0 is skipped, its logits are neither read nor written (they may hold NaN). Prompts go through an
+ *   index: with forced != NULL (int64 [n_forced][ld_forced], column j + 1 = prompt token j, -1 = free) row r is
+ *   forced to forced[prompt_idx[r]*ld_forced + p + 1] when p + 1 < ld_forced and that entry is a token of the
+ *   vocabulary; prompt_idx (int64 [R]) NULL, prompt_idx[r] < 0 or >= n_forced: the row has no prompt. So a slot
+ *   points at its image's row of ONE prompt table and admission copies no prompt. A row whose position lies
+ *   outside [0, ld_tok) is left as it is. For a row at row_pos[r] = p the edited row is bitwise what
+ *   mit_logits_constrain gives that row alone with *pos = p (forced row = that row's prompt). Columns V .. ld - 1,
+ *   tok, row_pos, done, the tables are not written.
+ * sample_pick_ragged: mit_sample_pick's filter and draw (same instantiations by V: weights in registers up to 1024
+ *   and 10240 keys, keys cached in LDS up to 12288, keys re-read beyond) at p = row_pos[r], the uniform being
+ *   uniforms[r] when uniforms != NULL, else the hash of (seed, row_id[r], p) -- mit_sample_uniform's rule with
+ *   row_id[r] (int64 [R]) for row0 + r. State: the one rule of greedy_pick_ragged above (done, limit, n_done; a
+ *   frozen row is neither read nor written, no PAD, row_pos[r] advances per row, a row with no room only retires);
+ *   there is no ticket and nothing crosses blocks. A live row that stores its token also does logprob[r] += l_tok -
+ *   lse and length[r] += 1 (either may be NULL). For a live row the token and the logprob increment are bitwise
+ *   what mit_sample_pick gives a one-row launch with row0 = row_id[r] and *pos = p.
+ * slot_admit_ex: mit_slot_admit (same copy, same resets, same range rule and counting) from records int64 [m][5]
+ *   = (slot, pool image, cap, row id, prompt index), which also writes row_id[slot], prompt_idx[slot], logprob[slot]
+ *   = 0 and length[slot] = 0 (row_id, prompt_idx int64 [slots], logprob f32, length int32; all required). An
+ *   out-of-range record writes none of them. mit_slot_admit keeps its ABI and behaviour. */
+int mit_logits_constrain_ragged(long R, long V, float* logits, long ld, const int64_t* tok, long ld_tok,
+                                const int64_t* row_pos, const int* done, float repetition_penalty, long no_repeat_ngram,
+                                long min_length, int64_t end_id, const int64_t* suppress, long n_suppress,
+                                const int64_t* forced, long ld_forced, long n_forced, const int64_t* prompt_idx,
+                                void* stream);
+int mit_sample_pick_ragged(long R, long V, const float* logits, long ld, float temperature, long top_k, float top_p,
+                           const uint64_t* seed, const int64_t* row_id, const float* uniforms, int64_t* ids, long ld_ids,
+                           int64_t* row_pos, int64_t end_id, const int64_t* limit, int* done, int* n_done,
+                           float* logprob, int* length, void* stream);
+int mit_slot_admit_ex(long m, const int64_t* records, long L, long S, long row_bytes, const void* pool_kv,
+                      long pool_images, void* kv, long slots, const float* pool_scale, float* scale, long n_scale,
+                      int64_t* ids, long ld_ids, int64_t start_id, int64_t* row_pos, int* done, int64_t* limit,
+                      int* n_done, int64_t* row_id, int64_t* prompt_idx, float* logprob, int* length, void* stream);
+
 /* Decode-step GEMM with the decoder's post-LN residual blocks folded in (bf16 only; the B-row GEMMs of
  * one token step, torch/nn/modules/transformer.py:1144-1153 norm_first=False):
  *   C[M, N] = act(A'[M, K] . B[N, K]^T + bias) (+ residual),  B = bf16 weights (nn.Linear layout)

@@ -4,6 +4,8 @@
 //
 //   mit_sample_uniform   the counter hash u(seed, row, position) the pick draws with (debug export)
 //   mit_sample_pick      filter, draw, write the token / log-probability / length / finished state; *pos += 1
+//   mit_sample_pick_ragged  the same filter and draw with one position PER ROW (rolling-batch decode): the uniform
+//                        of (seed, row_id[r], row_pos[r]), the state rule of mit_greedy_pick_ragged, no ticket
 //
 // One 256-thread block per row. The row's order keys (ord_f32, as beam.hip) sit in LDS up to kCap logits and are
 // re-read from global memory (L2) beyond that; up to 10240 logits (NC chunks of 4 per thread) the weights stay in
@@ -76,8 +78,11 @@ __global__ __launch_bounds__(256) void sample_uniform_kernel(long R, long row0, 
 }
 
 // NC > 0: the row has at most NC * 256 chunks; keys in LDS (NC * 1024 of them, zero past the row), weights in
-// registers. NC == 0: any V; keys in LDS when `cached`, else re-read; weights recomputed where they are used
-template <int NC>
+// registers. NC == 0: any V; keys in LDS when `cached`, else re-read; weights recomputed where they are used.
+// RAG: pos is row_pos [R], finished / n_finished are the rolling state's done / n_done, the row's stream is
+// row_id[r] and its room limit[r]; each row owns its position, so nothing crosses blocks (ticket unused). The
+// filter and the draw are one body: the same instructions in the same order under either flag.
+template <int NC, bool RAG>
 __global__ __launch_bounds__(256) void sample_pick_kernel(long V, const float* __restrict__ logits, long ld,
                                                           float tscale, long top_k, float top_p,
                                                           const uint64_t* __restrict__ seed, long row0,
@@ -85,13 +90,16 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(long V, const float* _
                                                           long ld_ids, int64_t* pos, int64_t end_id, int64_t pad_id,
                                                           int* __restrict__ finished, int* __restrict__ n_finished,
                                                           float* __restrict__ logprob, int* __restrict__ length,
-                                                          int* __restrict__ ticket, int cached) {
+                                                          int* __restrict__ ticket, int cached,
+                                                          const int64_t* __restrict__ row_id,
+                                                          const int64_t* __restrict__ limit) {
   extern __shared__ __attribute__((aligned(16))) uint32_t skey[];  // cached: the row's keys, zero past the row
   __shared__ uint32_t sred[2][4];
   __shared__ uint32_t sred2[2][4];
   const long r = blockIdx.x;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const long p = *pos;  // every block reads the position before it takes its ticket (below)
+  if (RAG && finished[r]) return;  // block-uniform; frozen: nothing of the row is read or written
+  const long p = RAG ? pos[r] : *pos;  // every block reads the position before it takes its ticket (below)
   const bool col_ok = p >= 0 && p + 1 < ld_ids;
 
   // *pos advances once, by the last block to take the ticket (mit_greedy_pick_advance's protocol): the
@@ -103,7 +111,7 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(long V, const float* _
       *ticket = 0;
     }
   };
-  if (finished[r]) {  // block-uniform; the row's logits are never read
+  if (!RAG && finished[r]) {  // block-uniform; the row's logits are never read
     if (tid == 0) {
       if (col_ok) ids[r * ld_ids + p + 1] = pad_id;
       take_ticket();
@@ -322,7 +330,7 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(long V, const float* _
                    __uint_as_float(sred[par][3]);
   par ^= 1;
   if (lane) base += prev;
-  const float u = uniforms ? uniforms[r] : sample_u(seed, row0 + r, p);
+  const float u = uniforms ? uniforms[r] : sample_u(seed, RAG ? (long)row_id[r] : row0 + r, p);
   const float mark = u * z2;
   uint32_t found = 0xFFFFFFFFu;  // the first token of the span whose running sum exceeds the mark
   int last = -1;                 // the span's largest kept token
@@ -359,6 +367,20 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(long V, const float* _
     // rounding left no crossing: the largest kept token; a row that kept nothing (NaN, all -inf): token 0
     long token = found != 0xFFFFFFFFu ? (long)found : (last >= 0 ? (long)last : 0);
     token = min(token, V - 1);
+    if constexpr (RAG) {  // mit_greedy_pick_ragged's rule (decode.hip ragged_pick_row); a row with no room only retires
+      const long lim = min((long)limit[r], ld_ids);
+      if (p >= 0 && p + 1 < lim) {
+        ids[r * ld_ids + p + 1] = token;
+        pos[r] = p + 1;
+        if (logprob) logprob[r] += row[token] - lse;
+        if (length) length[r] += 1;
+      }
+      if (token == end_id || p + 2 >= lim) {
+        finished[r] = 1;
+        atomicAdd(n_finished, 1);
+      }
+      return;
+    }
     if (col_ok) ids[r * ld_ids + p + 1] = token;
     if (logprob) logprob[r] += row[token] - lse;
     if (length) length[r] += 1;
@@ -402,9 +424,10 @@ extern "C" int mit_sample_pick(long R, long V, const float* logits, long ld, flo
   const long nkeys = ((V + 3) >> 2) << 2;
   const int cached = nkeys <= kCap;
 #define MIT_PICK_LAUNCH(NC_, LDS_, CACHED_)                                                                           \
-  hipLaunchKernelGGL(sample_pick_kernel<NC_>, dim3((unsigned)R), dim3(256), (size_t)(LDS_), (hipStream_t)stream, V,   \
-                     logits, ld, tscale, top_k, top_p, seed, row0, uniforms, ids, ld_ids, pos, end_id, pad_id,        \
-                     finished, n_finished, logprob, length, ticket, CACHED_)
+  hipLaunchKernelGGL((sample_pick_kernel<NC_, false>), dim3((unsigned)R), dim3(256), (size_t)(LDS_),                  \
+                     (hipStream_t)stream, V, logits, ld, tscale, top_k, top_p, seed, row0, uniforms, ids, ld_ids, pos, \
+                     end_id, pad_id, finished, n_finished, logprob, length, ticket, CACHED_,                          \
+                     (const int64_t*)nullptr, (const int64_t*)nullptr)
   // log2(e) / temperature, kept finite so that the maximum's (l - m) * tscale stays 0 at a denormal temperature
   const double ts = 1.4426950408889634 / (double)temperature;
   const float tscale = ts < 3.0e38 ? (float)ts : 3.0e38f;
@@ -416,5 +439,42 @@ extern "C" int mit_sample_pick(long R, long V, const float* logits, long ld, flo
     MIT_PICK_LAUNCH(0, cached ? nkeys * 4 : 0, cached);
 #undef MIT_PICK_LAUNCH
   MIT_LAUNCH_CHECK("mit_sample_pick");
+  return MIT_OK;
+}
+
+extern "C" int mit_sample_pick_ragged(long R, long V, const float* logits, long ld, float temperature, long top_k,
+                                      float top_p, const uint64_t* seed, const int64_t* row_id, const float* uniforms,
+                                      int64_t* ids, long ld_ids, int64_t* row_pos, int64_t end_id,
+                                      const int64_t* limit, int* done, int* n_done, float* logprob, int* length,
+                                      void* stream) {
+  MIT_CHECK_ARG(temperature > 0.f, "mit_sample_pick_ragged: temperature %g must be positive", (double)temperature);
+  MIT_CHECK_ARG(top_p > 0.f, "mit_sample_pick_ragged: top_p %g must be positive", (double)top_p);
+  MIT_CHECK_ARG(top_k >= 0, "mit_sample_pick_ragged: top_k %ld < 0", top_k);
+  MIT_CHECK_ARG(V >= 1 && V < (1L << 31), "mit_sample_pick_ragged: vocabulary %ld outside 1 .. 2^31 - 1", V);
+  MIT_CHECK_ARG(ld >= V, "mit_sample_pick_ragged: ld %ld < V %ld", ld, V);
+  MIT_CHECK_ARG(ld_ids >= 2, "mit_sample_pick_ragged: token rows need two columns at least");
+  MIT_CHECK_ARG(logits && ids && row_pos && limit && done && n_done, "mit_sample_pick_ragged: null pointer");
+  MIT_CHECK_ARG(uniforms || row_id, "mit_sample_pick_ragged: neither uniforms nor row_id");
+  MIT_CHECK_ARG(((uintptr_t)logits & 3) == 0, "mit_sample_pick_ragged: logits must be 4-B aligned");
+  MIT_CHECK_ARG(R >= 0 && R < (1L << 31), "mit_sample_pick_ragged: bad row count %ld", R);
+  MIT_RECORD([=]() { return mit_sample_pick_ragged(R, V, logits, ld, temperature, top_k, top_p, seed, row_id, uniforms, ids, ld_ids, row_pos, end_id, limit, done, n_done, logprob, length, stream); });
+  if (R == 0) return MIT_OK;
+  const long nkeys = ((V + 3) >> 2) << 2;
+  const int cached = nkeys <= kCap;
+#define MIT_PICK_LAUNCH(NC_, LDS_, CACHED_)                                                                           \
+  hipLaunchKernelGGL((sample_pick_kernel<NC_, true>), dim3((unsigned)R), dim3(256), (size_t)(LDS_),                   \
+                     (hipStream_t)stream, V, logits, ld, tscale, top_k, top_p, seed, 0L, uniforms, ids, ld_ids,       \
+                     row_pos, end_id, (int64_t)0, done, n_done, logprob, length, (int*)nullptr, CACHED_, row_id, limit)
+  // mit_sample_pick's scale and instantiation choice, so that a row's filter and draw are bitwise the same
+  const double ts = 1.4426950408889634 / (double)temperature;
+  const float tscale = ts < 3.0e38 ? (float)ts : 3.0e38f;
+  if (nkeys <= 1024)
+    MIT_PICK_LAUNCH(1, 1024 * 4, 1);
+  else if (nkeys <= 10240)
+    MIT_PICK_LAUNCH(10, 10240 * 4, 1);
+  else
+    MIT_PICK_LAUNCH(0, cached ? nkeys * 4 : 0, cached);
+#undef MIT_PICK_LAUNCH
+  MIT_LAUNCH_CHECK("mit_sample_pick_ragged");
   return MIT_OK;
 }

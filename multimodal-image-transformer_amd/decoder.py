@@ -509,10 +509,11 @@ class RollingState(DecodeState):
     may hold). A pool of `pool` images' cross-attention K/V (pool_kv, or pool_kv8 + pool_scale with kv_dtype "fp8")
     feeds the slots: mit_slot_admit copies an image's rows into a slot and resets the slot. Every slot starts EMPTY:
     done = 1, n_done = slots, K/V (and scales) zero, ids[:, 0] = START, so stepping an empty slot is finite
-    arithmetic whose results nobody reads."""
+    arithmetic whose results nobody reads. stream (a dict of _stream_init's arguments; None: nothing more is
+    allocated) opts into the state of sampled / constrained rolling decode."""
 
     def __init__(self, dec: "TransformerDecoder", slots: int, S: int, max_len: int, start_id: int, end_id: int,
-                 pool: Optional[int] = None, kv_dtype: Optional[str] = None):
+                 pool: Optional[int] = None, kv_dtype: Optional[str] = None, stream: Optional[dict] = None):
         # no shared position: pos / finished / n_finished stay None, so no scalar-pos launch can be given one
         super().__init__(dec, slots, S, max_len, start_id, end_id, kv_dtype=kv_dtype, shared_pos=False)
         dev = dec.device
@@ -550,6 +551,54 @@ class RollingState(DecodeState):
             self.rows_host = self.rows_host.pin_memory()
         if dev.type == "cuda":
             self.triples_host = self.triples_host.pin_memory()
+        self.stream = False
+        if stream is not None:
+            self._stream_init(dec, **stream)
+
+    def _stream_init(self, dec, temperature=None, top_k=0, top_p=1.0, seed=0, constraints=None, prompt_table=None):
+        """The opt-in state of sampled / constrained rolling decode (TransformerDecoder.rolling_stream_begin): per slot
+        the global row id its random stream hangs on, the row of the prompt table its forced tokens come from (-1:
+        none), the cumulative log-probability and the generated length -- all (re)set by mit_slot_admit_ex from
+        records (slot, pool image, cap, row id, prompt index) -- plus the device seed, the filter settings, the
+        prompt table (int64 [n, Lp + 1], DecodeState.forced's layout, one row per prompt) and the suppress list.
+        A harvest takes the ids rows and the log-probabilities in one packed copy."""
+        dev, slots = dec.device, self.slots
+        self.stream = True
+        self.temperature = None if temperature is None else float(temperature)
+        self.top_k, self.top_p = int(top_k), float(top_p)
+        self.row_id = torch.zeros(slots, dtype=torch.int64, device=dev)
+        self.prompt_idx = torch.full((slots,), -1, dtype=torch.int64, device=dev)
+        self.logprob = torch.zeros(slots, dtype=torch.float32, device=dev)
+        self.length = torch.zeros(slots, dtype=torch.int32, device=dev)
+        s = int(seed) & 0xFFFFFFFFFFFFFFFF  # the kernels read a uint64
+        self.seed = torch.tensor([s - (1 << 64) if s >= (1 << 63) else s], dtype=torch.int64, device=dev)
+        if constraints is not None and constraints.active():
+            self.cons = constraints
+            if constraints.suppress:
+                self.suppress = torch.tensor(constraints.suppress, dtype=torch.int64, device=dev)
+            if prompt_table is not None:
+                self.forced = prompt_table.contiguous().to(dev)
+        self.records = torch.zeros(slots, 5, dtype=torch.int64, device=dev)
+        self.records_host = torch.zeros(slots, 5, dtype=torch.int64)
+        self.pack_dev = torch.empty(slots, self.max_len + 1, dtype=torch.int64, device=dev)
+        self.pack_host = torch.empty(slots, self.max_len + 1, dtype=torch.int64)
+        if dev.type == "cuda":
+            self.records_host = self.records_host.pin_memory()
+            self.pack_host = self.pack_host.pin_memory()
+
+    def harvest_ex(self, slot_list):
+        """harvest for the opt-in state: (ids rows [n, max_len] on the host, the n log-probabilities), packed on the
+        device (ids | the f32 bits of logprob) and taken in ONE stream-ordered copy, waited for before the admit
+        launch that reuses the slots."""
+        n, T = len(slot_list), self.max_len
+        self.rows_idx[:n].copy_(torch.tensor(slot_list, dtype=torch.int64), non_blocking=True)
+        idx = self.rows_idx[:n]
+        self.pack_dev[:n, :T] = self.ids.index_select(0, idx)
+        self.pack_dev[:n, T] = self.logprob.index_select(0, idx).view(torch.int32)
+        self.pack_host[:n].copy_(self.pack_dev[:n], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        lp = self.pack_host[:n, T].to(torch.int32).view(torch.float32).tolist()
+        return self.pack_host[:n, :T], lp
 
     def harvest(self, slot_list):
         """The ids rows of the given slots, [len(slot_list), max_len] on the host (pinned): only those rows are
@@ -1340,6 +1389,93 @@ class TransformerDecoder:
         native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
         native.greedy_pick_ragged(stt.logits, stt.ids, stt.row_pos, stt.end_id, stt.limit, stt.done, stt.n_done,
                                   V=self.V)
+
+    # --- rolling-batch decode, sampled and constrained (mit_*_ragged of constrain.hip / sample.hip) ------
+    def rolling_stream_begin(self, S: int, slots: int, max_len: int, start_id: int, end_id: int,
+                             pool: Optional[int] = None, kv_dtype: Optional[str] = None,
+                             temperature: Optional[float] = None, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                             constraints: Optional[DecodeConstraints] = None,
+                             prompt_table: Optional[torch.Tensor] = None) -> "RollingState":
+        """rolling_begin with the opt-in state of sampled / constrained decode (RollingState._stream_init).
+        temperature None: greedy picks. constraints: the row-independent settings (penalty, n-gram, minimum length,
+        suppress list); prompts come as prompt_table (int64 [n, Lp + 1], column j + 1 = prompt token j, -1 = free),
+        which a slot's prompt_idx points into. Slots are admitted with rolling_admit_ex and stepped with
+        rolling_stream_step."""
+        if max_len > self.pe.shape[0]:
+            raise ValueError(f"max_len {max_len} exceeds the positional table ({self.pe.shape[0]} = "
+                             f"decoder_max_seq_len; the reference's PositionalEncoding would fail too)")
+        if slots < 1 or (pool is not None and pool < 1):
+            raise ValueError(f"rolling decode needs slots >= 1 and pool >= 1 (got {slots}, {pool})")
+        if max_len < 2:
+            raise ValueError("rolling decode needs max_len >= 2 (a cap of 1 takes no slot)")
+        if temperature is not None and (not temperature > 0 or not top_p > 0 or top_k < 0):
+            raise ValueError(f"sampling needs temperature > 0, top_p > 0 and top_k >= 0 (got {temperature}, {top_p}, "
+                             f"{top_k})")
+        return RollingState(self, slots, S, max_len, start_id, end_id, pool=pool, kv_dtype=kv_dtype,
+                            stream=dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                        constraints=constraints, prompt_table=prompt_table))
+
+    def rolling_admit_ex(self, stt: "RollingState", records):
+        """rolling_admit for the opt-in state: one mit_slot_admit_ex launch for the (slot, pool entry, cap, row id,
+        prompt index) records, which also resets each slot's row id, prompt index, log-probability and length."""
+        m = len(records)
+        if m == 0:
+            return
+        n_prompts = stt.forced.shape[0] if stt.forced is not None else 0
+        for s_, e_, c_, _r, pi in records:
+            if not (0 <= s_ < stt.slots and 0 <= e_ < stt.pool and 2 <= c_ <= stt.max_len and pi < n_prompts):
+                raise ValueError(f"rolling_admit_ex: bad record (slot {s_}, pool entry {e_}, cap {c_}, prompt {pi})")
+        if len({t[0] for t in records}) != m:
+            raise ValueError("rolling_admit_ex: a slot is named twice")
+        if stt.triples_ev is not None:  # the previous admission's copy out of the pinned records has run
+            stt.triples_ev.synchronize()
+        stt.records_host[:m] = torch.tensor(records, dtype=torch.int64)
+        stt.records[:m].copy_(stt.records_host[:m], non_blocking=True)
+        if stt.records_host.is_pinned():
+            stt.triples_ev = torch.cuda.Event()
+            stt.triples_ev.record()
+        fp8 = stt.kv8 is not None
+        native.slot_admit_ex(stt.records, m, stt.pool_kv8 if fp8 else stt.pool_kv, stt.kv8 if fp8 else stt.kv, stt.S,
+                             stt.pool_scale, stt.kv_scale, stt.ids, stt.start_id, stt.row_pos, stt.done, stt.limit,
+                             stt.n_done, stt.row_id, stt.prompt_idx, stt.logprob, stt.length)
+
+    def _rolling_logits(self, stt: "RollingState"):
+        """The step's body and the head as a plain GEMM into f32 logits (as sample_step / _decode_step_constrained),
+        then, with active constraints, their per-row launch."""
+        x = self._step_body_fused(stt) if stt.fused else self._step_body(stt)
+        st, w = self.store, self.store.w
+        native.linear(x, w("fc_out.weight"), stt.logits, bias=st.p("fc_out.bias"))
+        c = stt.cons
+        if c is not None:
+            native.logits_constrain_ragged(stt.logits, self.V, stt.ids, stt.row_pos, done=stt.done,
+                                           repetition_penalty=c.repetition_penalty, no_repeat_ngram=c.no_repeat_ngram,
+                                           min_length=c.min_length, end_id=stt.end_id, suppress=stt.suppress,
+                                           forced=stt.forced, prompt_idx=stt.prompt_idx)
+
+    def rolling_sample_step(self, stt: "RollingState"):
+        """One sampled token for every slot that is not done, each at its own position and from its own random
+        stream (seed, row_id[b], row_pos[b]); a done (or empty) slot is frozen. The launch list does not depend on
+        the state, so one recording replays between admissions."""
+        self._rolling_logits(stt)
+        native.sample_pick_ragged(stt.logits, self.V, stt.temperature, stt.top_k, stt.top_p, stt.seed, stt.row_id, None,
+                                  stt.ids, stt.row_pos, stt.end_id, stt.limit, stt.done, stt.n_done, stt.logprob,
+                                  stt.length)
+
+    def rolling_step_constrained(self, stt: "RollingState"):
+        """rolling_step with active constraints: the folded argmax of the fused head gives way to f32 logits in
+        memory, which the per-row constraint launch edits before the ragged pick reads them."""
+        self._rolling_logits(stt)
+        native.greedy_pick_ragged(stt.logits, stt.ids, stt.row_pos, stt.end_id, stt.limit, stt.done, stt.n_done,
+                                  V=self.V)
+
+    def rolling_stream_step(self, stt: "RollingState"):
+        """The token step of an opt-in state: sampled when it has a temperature, else greedy -- constrained when
+        constraints are active, else rolling_step itself."""
+        if stt.temperature is not None:
+            return self.rolling_sample_step(stt)
+        if stt.cons is not None:
+            return self.rolling_step_constrained(stt)
+        return self.rolling_step(stt)
 
     # --- beam search on the same step (csrc/beam.hip) ---------------------------------------------------
     def beam_begin(self, mem: torch.Tensor, mem_ld: int, S: int, B: int, K: int, max_len: int, start_id: int,

@@ -65,7 +65,7 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
                       length_penalty: float = 0.0, temperature: Optional[float] = None, top_k: int = 0,
                       top_p: float = 1.0, seed: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                       min_length: int = 0, suppress_tokens=(), prompts=None, kv_dtype: Optional[str] = None,
-                      rolling_slots: Optional[int] = None):
+                      rolling_slots: Optional[int] = None, stream_slots: Optional[int] = None):
     """Captions for a list of PIL images / HWC arrays or a [B,3,H,W] pixel tensor, `batch_size` images
     per batched decode. Returns [(processed ids, text)] — text is None without a `decode` function
     (the BPE tokenizer, tokenizer.py, is a host-side library outside this path).
@@ -83,7 +83,34 @@ def generate_captions(model, images, decode: Optional[Callable[[List[int]], str]
     rolling_slots: a number decodes greedily with rolling batching (generate_rolling_iter: that many decode slots,
     a finished caption's slot handed to the next image; `batch_size` images per encoder chunk): the same
     (ids, text) list, sooner when the captions' lengths differ. It excludes beam_size, temperature and every decode
-    constraint."""
+    constraint.
+    stream_slots: a number decodes with rolling batching on that many slots whatever the request is -- greedy,
+    sampled (temperature, top_k, top_p, seed; one sample per image) or constrained (every constraint above, prompts
+    per image included) -- through generate_stream_iter; `batch_size` images per encoder chunk. The (ids, text) list
+    is the one the batch_size path returns. It excludes beam_size and rolling_slots."""
+    if stream_slots is not None:
+        if beam_size is not None:
+            raise ValueError("generate_captions: stream_slots decodes greedily or by sampling; it excludes beam_size "
+                             "(the beams of an image interact)")
+        if rolling_slots is not None:
+            raise ValueError("generate_captions: choose rolling_slots or stream_slots, not both")
+        if isinstance(images, torch.Tensor):
+            pv = images if images.dim() == 4 else images.unsqueeze(0)
+        else:
+            pv = model.image_processor(images=list(images), return_tensors="pt")["pixel_values"]
+        kw = dict(slots=stream_slots, encode_batch=batch_size, temperature=temperature, top_k=top_k, top_p=top_p,
+                  seed=seed, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                  min_length=min_length, suppress_tokens=tuple(suppress_tokens or ()), prompts=prompts)
+        if kv_dtype is not None:
+            kw["kv_dtype"] = kv_dtype
+        got = {i: ids for i, _, ids, _ in
+               model.generate_stream_iter((pv[i:i + batch_size] for i in range(0, pv.shape[0], batch_size)),
+                                          start_token_id, end_token_id, max_len=max_len, **kw)}
+        out = []
+        for i in range(pv.shape[0]):
+            p = postprocess_ids(got[i], start_token_id, end_token_id)
+            out.append((p, clean_text(decode(p)) if decode is not None else None))
+        return out
     if rolling_slots is not None:
         if beam_size is not None or temperature is not None or repetition_penalty != 1.0 or no_repeat_ngram_size \
                 or min_length or suppress_tokens or prompts:
@@ -230,6 +257,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--rolling_slots", type=int, default=None,
                     help="greedy decode with rolling batching on this many slots: a finished caption's slot goes to "
                          "the next image (excludes --beam_size, --temperature and the constraints)")
+    ap.add_argument("--stream_slots", type=int, default=None,
+                    help="rolling batching on this many slots for greedy, sampled (--temperature) and constrained "
+                         "requests alike (excludes --beam_size and --rolling_slots)")
     ap.add_argument("--score_file", default=None,
                     help="score instead of generating: a JSON file holding one list of candidate id lists (scored "
                          "against every image) or one such list per image; prints each image's ranking")
@@ -264,6 +294,8 @@ def decode_options(args) -> dict:
         o["kv_dtype"] = args.kv_dtype
     if args.rolling_slots is not None:
         o["rolling_slots"] = args.rolling_slots
+    if args.stream_slots is not None:
+        o["stream_slots"] = args.stream_slots
     return o
 
 
@@ -272,6 +304,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.temperature is not None and args.beam_size is not None:
         ap.error("--beam_size and --temperature exclude each other")
+    if args.stream_slots is not None and (args.beam_size is not None or args.rolling_slots is not None):
+        ap.error("--stream_slots excludes --beam_size and --rolling_slots")
     if args.score_file is not None and (args.temperature is not None or args.beam_size is not None):
         ap.error("--score_file scores given captions: it excludes --beam_size and --temperature")
     from PIL import Image

@@ -826,6 +826,158 @@ class ImageToTextModel:
                 for r, (_, image, n_ids) in enumerate(harvest):
                     yield image, rows[r, :n_ids].tolist()
 
+    # --- rolling-batch captioning, sampled and constrained (decoder.rolling_stream_begin / rolling_stream_step) ------
+    def generate_stream_iter(self, batches, start_token_id: int, end_token_id: int, max_len: int = 100, *,
+                             slots: int = 256, temperature: Optional[float] = None, top_k: int = 0, top_p: float = 1.0,
+                             num_samples: int = 1, seed: int = 0, image_offset: int = 0,
+                             repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_length: int = 0,
+                             suppress_tokens=(), prompts=None, max_lens=None, check_every: Optional[int] = None,
+                             kv_dtype: Optional[str] = None, use_graph: bool = True,
+                             encode_batch: Optional[int] = None, pool: Optional[int] = None,
+                             streams: Optional[int] = None, beam_size: Optional[int] = None,
+                             method: Optional[str] = None):
+        """Captions of a stream of images with rolling batching (generate_rolling_iter's schedule: `slots` decode
+        rows, each at its own position, a finished row's slot handed to the next work item) for greedy, SAMPLED and
+        CONSTRAINED decoding. Yields (image, sample, ids, logprob) in COMPLETION order.
+
+        temperature None: greedy (num_samples must be 1, logprob is None); the ids are generate_batch's for that
+        image under the same constraints. temperature > 0: num_samples rows per image, drawn as
+        generate_sample_batch draws them -- sample n of image i at position p uses the counter hash of (seed,
+        (image_offset + i) * num_samples + n, p), whatever slot it sits in and whenever it was admitted -- so ids and
+        logprob are generate_sample_batch's for the same seed, num_samples and global image index, bit for bit
+        (while both run the same GEMM family). An image's samples share one pool entry of
+        cross-attention K/V and each takes its own slot (one admit copy per sample).
+
+        repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts: generate_batch's constraints
+        (csrc/constrain.hip mit_logits_constrain_ragged: every row at its own position). prompts: one token list for
+        all images, or one list per image indexed by image number (arrival order from 0, as max_lens); a slot reads
+        its image's row of one prompt table. max_lens, check_every, kv_dtype, use_graph, encode_batch, pool: as
+        generate_rolling_iter.
+
+        Raises ValueError before any launch, from this call and not from the first next(): beams (beam_size or
+        method "beam": the beams of an image interact), streams > 1, bad sampling parameters, greedy with
+        num_samples != 1, bad constraint settings, caps outside [1, max_len], kv_dtype "fp8" on a float32 model.
+        Per-image prompts and the number of caps are checked chunk by chunk, before that chunk's launches."""
+        dec = self.decoder
+        if (beam_size is not None and int(beam_size) > 1) or method == "beam":
+            raise ValueError("stream decode does not run beam search: the beams of an image interact through the "
+                             "selection and the ancestor table (use generate_beam_batch)")
+        if method not in (None, "greedy", "sample"):
+            raise ValueError(f"method {method!r}: stream decode is greedy (temperature None) or sampled")
+        if streams is not None and int(streams) > 1:
+            raise ValueError("stream decode runs one row group (streams > 1 is generate_batch's)")
+        if int(slots) < 1:
+            raise ValueError(f"stream decode needs slots >= 1 (got {slots})")
+        N = int(num_samples)
+        if N < 1:
+            raise ValueError(f"num_samples {N} must be at least 1")
+        if temperature is None:
+            if N != 1:
+                raise ValueError(f"greedy stream decode (temperature None) yields one caption per image, not {N}")
+        elif not temperature > 0 or not top_p > 0 or top_k < 0:
+            raise ValueError(f"sampling needs temperature > 0, top_p > 0 and top_k >= 0 (got {temperature}, {top_p}, "
+                             f"{top_k})")
+        if int(image_offset) < 0:
+            raise ValueError(f"image_offset {image_offset} < 0")
+        if max_len < 1 or max_len > dec.pe.shape[0]:
+            raise ValueError(f"max_len {max_len} must be in 1..{dec.pe.shape[0]} (the positional table, "
+                             f"decoder_max_seq_len)")
+        if max_lens is not None:
+            max_lens = [int(c) for c in max_lens]
+            bad = [(i, c) for i, c in enumerate(max_lens) if not 1 <= c <= max_len]
+            if bad:
+                raise ValueError(f"max_lens must lie in 1..{max_len}: image {bad[0][0]} has {bad[0][1]}")
+        cons = DecodeConstraints(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, prompts)
+        # the settings every row shares (and a prompt for all images) now; a prompt list per image chunk by chunk
+        DecodeConstraints(repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens,
+                          None if cons.per_image() else cons.prompts).validate(dec.V, int(max_len), int(end_token_id), 1)
+        resolve_kv_dtype(kv_dtype, self.dtype)
+        sch = rolling.RollingScheduler(int(slots), check_every, encode_batch, pool, samples=N)
+        self.last_rolling_schedule = sch
+        return self._stream_run(sch, batches, int(start_token_id), int(end_token_id), int(max_len), max_lens, kv_dtype,
+                                use_graph, cons, temperature, int(top_k), float(top_p), int(seed), int(image_offset))
+
+    def generate_stream(self, batches, start_token_id: int, end_token_id: int, max_len: int = 100, *,
+                        return_logprob: bool = False, **kwargs):
+        """generate_stream_iter collected, in input order. Sampling (temperature given): generate_sample_batch's
+        shapes for the concatenated images -- per image its ids when num_samples == 1 and return_logprob is False,
+        else its num_samples (ids, logprob) pairs. Greedy: generate_batch's list of ids."""
+        N = int(kwargs.get("num_samples", 1))
+        sampled = kwargs.get("temperature") is not None
+        got = {(i, n): (ids, lp) for i, n, ids, lp in
+               self.generate_stream_iter(batches, start_token_id, end_token_id, max_len, **kwargs)}
+        B = len(got) // N
+        if not sampled or (N == 1 and not return_logprob):
+            return [got[(i, 0)][0] for i in range(B)]
+        return [[got[(i, n)] for n in range(N)] for i in range(B)]
+
+    @torch.no_grad()
+    def _stream_run(self, sch, batches, start_id, end_id, max_len, max_lens, kv_dtype, use_graph, cons, temperature,
+                    top_k, top_p, seed, image_offset):
+        self.eval()
+        dec = self.decoder
+        N = sch.samples
+        source = self._rolling_chunks(batches, sch.encode_batch)
+        stt, run = None, None
+        launch = os.environ.get("MIT_DECODE_LAUNCH", "plan") if use_graph else "eager"
+        per_image = cons.per_image() and cons.has_prompts()
+        shared = cons.has_prompts() and not per_image
+        table = None
+        if cons.has_prompts():  # one table for the whole run: row i = image i's prompt (or row 0 = everybody's)
+            rows = cons.prompts if per_image else [cons.prompts]
+            table = torch.full((len(rows), max(len(p) for p in rows) + 1), -1, dtype=torch.int64)
+            for b, p in enumerate(rows):
+                table[b, 1:1 + len(p)] = torch.tensor(p, dtype=torch.int64)
+        none_lp = None if temperature is None else 0.0
+        while True:
+            while True:  # chunks and admissions until no free slot is left that the source could fill
+                while sch.wants_chunk():
+                    pv = next(source, None)
+                    if pv is None:
+                        sch.close()
+                        break
+                    n, i0 = pv.shape[0], sch.next_image
+                    if max_lens is not None and i0 + n > len(max_lens):
+                        raise ValueError(f"max_lens holds {len(max_lens)} caps, the source at least {i0 + n} images")
+                    if per_image:
+                        if i0 + n > len(cons.prompts):
+                            raise ValueError(f"prompts holds {len(cons.prompts)} lists, the source at least {i0 + n} "
+                                             f"images")
+                        DecodeConstraints(prompts=cons.prompts[i0:i0 + n]).validate(dec.V, max_len, end_id, n)
+                    caps = max_lens[i0:i0 + n] if max_lens is not None else [max_len] * n
+                    at, trivial = sch.add_chunk(caps)
+                    if len(trivial) < n:  # some image of the chunk needs a slot: encode it, K/V into the pool
+                        mem, mem_ld, S, _, _ = self._encode_memory(pv.to(self.device).float())
+                        if stt is None:
+                            stt = dec.rolling_stream_begin(S, sch.slots, max(max_len, 2), start_id, end_id,
+                                                           pool=sch.pool, kv_dtype=kv_dtype, temperature=temperature,
+                                                           top_k=top_k, top_p=top_p, seed=seed, constraints=cons,
+                                                           prompt_table=table)
+                            dec.rolling_stream_step(stt)  # every slot is empty: warms every kernel, moves nothing
+                            if launch in ("plan", "graph"):
+                                run = native.record(lambda: dec.rolling_stream_step(stt)).run
+                            else:
+                                run = lambda: dec.rolling_stream_step(stt)  # noqa: E731
+                        dec.rolling_fill(stt, mem, mem_ld, S, n, at)
+                    for i in trivial:
+                        for k in range(N):
+                            yield i, k, [start_id], none_lp
+                records = [(s, entry, cap, image_offset * N + row, (row // N) if per_image else (0 if shared else -1))
+                           for s, entry, cap, row in sch.admissions_ex()]
+                if records:  # launched before the next chunk may overwrite the pool region it reads
+                    dec.rolling_admit_ex(stt, records)
+                if not (records and sch.wants_chunk()):
+                    break
+            if sch.finished():
+                return
+            for _ in range(sch.next_steps()):
+                run()
+            harvest = sch.poll(*stt.snapshot())
+            if harvest:
+                rows, lps = stt.harvest_ex([h[0] for h in harvest])  # before the slots are reused
+                for r, (_, row, n_ids) in enumerate(harvest):
+                    yield row // N, row % N, rows[r, :n_ids].tolist(), (None if temperature is None else lps[r])
+
     @torch.no_grad()
     def generate_beam_batch(self, images, start_token_id: int, end_token_id: int, max_len: int = 100,
                             beam_size: int = config.BEAM_SIZE, length_penalty: float = 0.0, return_all: bool = False,

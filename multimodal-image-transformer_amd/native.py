@@ -200,6 +200,11 @@ SIGNATURES = {
     "mit_greedy_pick_ragged": (I, [L, L, vp, L, vp, L, vp, ctypes.c_int64, vp, vp, vp, vp]),
     "mit_greedy_pick_keys_ragged": (I, [L, vp, vp, L, vp, ctypes.c_int64, vp, vp, vp, vp]),
     "mit_slot_admit": (I, [L, vp, L, L, L, vp, L, vp, L, vp, vp, L, vp, L, ctypes.c_int64, vp, vp, vp, vp, vp]),
+    "mit_logits_constrain_ragged": (I, [L, L, vp, L, vp, L, vp, vp, Fl, L, L, ctypes.c_int64, vp, L, vp, L, L, vp, vp]),
+    "mit_sample_pick_ragged": (I, [L, L, vp, L, Fl, L, Fl, vp, vp, vp, vp, L, vp, ctypes.c_int64, vp, vp, vp, vp, vp,
+                                   vp]),
+    "mit_slot_admit_ex": (I, [L, vp, L, L, L, vp, L, vp, L, vp, vp, L, vp, L, ctypes.c_int64, vp, vp, vp, vp, vp, vp,
+                              vp, vp, vp]),
 }
 
 
@@ -1014,6 +1019,44 @@ def slot_admit(triples, m, pool_kv, kv, S, pool_scale, scale, ids, start_id, row
                                 kv.shape[1] // S, ptr(pool_scale), ptr(scale),
                                 scale.shape[2] if scale is not None else 0, ptr(ids), ids.shape[1], int(start_id),
                                 ptr(row_pos), ptr(done), ptr(limit), ptr(n_done), stream_ptr()), "mit_slot_admit")
+
+
+def slot_admit_ex(records, m, pool_kv, kv, S, pool_scale, scale, ids, start_id, row_pos, done, limit, n_done, row_id,
+                  prompt_idx, logprob, length):
+    """slot_admit from records int64 [>= m, 5] on the device, (slot, pool image, cap, row id, prompt index), which
+    also writes row_id / prompt_idx / logprob = 0 / length = 0 of each admitted slot (mit_slot_admit_ex)."""
+    L = kv.shape[0]
+    row_bytes = kv.shape[2] * kv.element_size()
+    _check(lib().mit_slot_admit_ex(m, ptr(records), L, S, row_bytes, ptr(pool_kv), pool_kv.shape[1] // S, ptr(kv),
+                                   kv.shape[1] // S, ptr(pool_scale), ptr(scale),
+                                   scale.shape[2] if scale is not None else 0, ptr(ids), ids.shape[1], int(start_id),
+                                   ptr(row_pos), ptr(done), ptr(limit), ptr(n_done), ptr(row_id), ptr(prompt_idx),
+                                   ptr(logprob), ptr(length), stream_ptr()), "mit_slot_admit_ex")
+
+
+def sample_pick_ragged(logits, V, temperature, top_k, top_p, seed, row_id, uniforms, ids, row_pos, end_id, limit, done,
+                       n_done, logprob, length):
+    """One sampled token per row that is not done, each at its own position (mit_sample_pick_ragged): sample_pick's
+    filter and draw from `uniforms` (f32 [R]) or the (seed, row_id[r], row_pos[r]) hash, then greedy_pick_ragged's
+    state rule; logprob += log-softmax of the pick and length += 1 for the rows that stored a token."""
+    _check(lib().mit_sample_pick_ragged(logits.shape[0], V, ptr(logits), logits.stride(0), float(temperature),
+                                        int(top_k), float(top_p), ptr(seed), ptr(row_id), ptr(uniforms), ptr(ids),
+                                        ids.stride(0), ptr(row_pos), int(end_id), ptr(limit), ptr(done), ptr(n_done),
+                                        ptr(logprob), ptr(length), stream_ptr()), "mit_sample_pick_ragged")
+
+
+def logits_constrain_ragged(logits, V, tok, row_pos, *, done=None, repetition_penalty=1.0, no_repeat_ngram=0,
+                            min_length=0, end_id=-1, suppress=None, forced=None, prompt_idx=None):
+    """logits_constrain with one position per row (mit_logits_constrain_ragged): row r's history is tok[r, 0 ..
+    row_pos[r]], rows with done[r] != 0 are skipped, and row r's forced tokens are row prompt_idx[r] of the prompt
+    table `forced` (int64 [n, ld_forced]; a negative index: no prompt)."""
+    _check(lib().mit_logits_constrain_ragged(logits.shape[0], V, ptr(logits), logits.stride(0), ptr(tok), tok.stride(0),
+                                             ptr(row_pos), ptr(done), float(repetition_penalty), int(no_repeat_ngram),
+                                             int(min_length), int(end_id), ptr(suppress),
+                                             suppress.numel() if suppress is not None else 0, ptr(forced),
+                                             forced.stride(0) if forced is not None else 0,
+                                             forced.shape[0] if forced is not None else 0, ptr(prompt_idx),
+                                             stream_ptr()), "mit_logits_constrain_ragged")
 
 
 # --- beam-search decoding (beam.hip) ---------------------------------------------------------------

@@ -18,6 +18,11 @@ needed a slot has been admitted (admission copies the entry's K/V into the slot)
         if sch.finished(): break
         run sch.next_steps() token steps
         sch.poll(done, row_pos) -> (slot, image, n_ids)      # newly done: copy their ids BEFORE the next admissions
+
+samples = N > 1 (ImageToTextModel.generate_stream_iter): an image that needs a slot becomes N work items that share
+its one pool entry; item n of image i has the row id i * N + n, takes its own slot (admissions_ex names the row id;
+poll returns it in the place of the image) and the region is free once all the items of its images are admitted.
+With samples = 1 an item is its image and nothing changes.
 """
 from collections import deque
 from typing import List, Optional, Sequence, Tuple
@@ -27,7 +32,7 @@ CHECK_EVERY_DEFAULT = 2  # of 1 / 2 / 4 / 8 the best median on the ragged benchm
 
 class RollingScheduler:
     def __init__(self, slots: int, check_every: Optional[int] = None, encode_batch: Optional[int] = None,
-                 pool: Optional[int] = None):
+                 pool: Optional[int] = None, samples: int = 1):
         check_every = CHECK_EVERY_DEFAULT if check_every is None else int(check_every)
         encode_batch = slots if encode_batch is None else int(encode_batch)
         if slots < 1:
@@ -36,15 +41,19 @@ class RollingScheduler:
             raise ValueError(f"check_every must be at least 1 (got {check_every})")
         if encode_batch < 1:
             raise ValueError(f"encode_batch must be at least 1 (got {encode_batch})")
+        if int(samples) < 1:
+            raise ValueError(f"samples must be at least 1 (got {samples})")
+        self.samples = int(samples)
         pool = max(slots, encode_batch) // encode_batch * encode_batch if pool is None else int(pool)
         if pool < encode_batch or pool % encode_batch:
             raise ValueError(f"the pool ({pool}) must be a positive multiple of encode_batch ({encode_batch})")
         self.slots, self.check_every, self.encode_batch, self.pool = slots, check_every, encode_batch, pool
-        self.slot_image: List[Optional[int]] = [None] * slots  # the image a slot decodes, None: empty / harvested
+        # the image a slot decodes (with samples > 1: the row id image * samples + n), None: empty / harvested
+        self.slot_image: List[Optional[int]] = [None] * slots
         self.slot_cap = [0] * slots
         self.slot_pos = [0] * slots                            # row_pos of the slot at the last poll
-        self.ready = deque()                                   # (image, pool entry, cap): K/V in the pool, no slot yet
-        self.region_left = [0] * (pool // encode_batch)        # images of a region still waiting for a slot
+        self.ready = deque()                                   # (item, pool entry, cap): K/V in the pool, no slot yet
+        self.region_left = [0] * (pool // encode_batch)        # items of a region still waiting for a slot
         self.fill_region = 0
         self.next_image = 0
         self.exhausted = False
@@ -77,8 +86,9 @@ class RollingScheduler:
             if cap == 1:
                 trivial.append(self.next_image + j)
             else:
-                self.ready.append((self.next_image + j, at + j, int(cap)))
-                self.region_left[r] += 1
+                for n_ in range(self.samples):
+                    self.ready.append(((self.next_image + j) * self.samples + n_, at + j, int(cap)))
+                self.region_left[r] += self.samples
         self.next_image += n
         self.fill_region = (r + 1) % len(self.region_left)
         self.chunks += 1
@@ -92,6 +102,10 @@ class RollingScheduler:
     def admissions(self) -> List[Tuple[int, int, int]]:
         """(slot, pool entry, cap) for every free slot that a ready image can take, in slot order; the slots are
         occupied from here on."""
+        return [t[:3] for t in self.admissions_ex()]
+
+    def admissions_ex(self) -> List[Tuple[int, int, int, int]]:
+        """admissions() with the item admitted: (slot, pool entry, cap, row id = image * samples + n)."""
         out = []
         for s in self.free_slots():
             if not self.ready:
@@ -99,7 +113,7 @@ class RollingScheduler:
             image, entry, cap = self.ready.popleft()
             self.slot_image[s], self.slot_cap[s], self.slot_pos[s] = image, cap, 0
             self.region_left[entry // self.encode_batch] -= 1
-            out.append((s, entry, cap))
+            out.append((s, entry, cap, image))
         if out:
             self.admits += 1
         return out
@@ -114,7 +128,8 @@ class RollingScheduler:
 
     def poll(self, done: Sequence[int], row_pos: Sequence[int]) -> List[Tuple[int, int, int]]:
         """A snapshot of the device's done flags and positions. Returns (slot, image, n_ids) for every occupied slot
-        seen done: its caption is ids[slot, :n_ids], to be copied before the slot is reused; the slot is free."""
+        seen done: its caption is ids[slot, :n_ids], to be copied before the slot is reused; the slot is free. With
+        samples > 1 `image` is the item's row id (image, n = divmod(row id, samples))."""
         self.polls += 1
         out = []
         for s, image in enumerate(self.slot_image):
