@@ -416,6 +416,25 @@ int mit_adamw(long n, float* param, const float* grad, float* m, float* v, void*
               const float* lr, const int64_t* step, float beta1, float beta2, float eps, float weight_decay,
               void* stream);
 
+/* Gradient accumulation over micro-batches (additive since ABI 9): the backward WRITES the flat f32 gradient
+ * buffer, so an optimizer step over k micro-batches sums them through a second flat buffer `acc` of the same n:
+ *   MIT_ACC_FIRST  acc[i]  = grad[i]            first micro-batch (acc needs no zero-fill, ever)
+ *   MIT_ACC_ADD    acc[i]  = acc[i] + grad[i]   middle micro-batches
+ *   MIT_ACC_LAST   grad[i] = acc[i] + grad[i]   last micro-batch: the total lands in `grad` itself, so mit_grad_norm,
+ *                                               mit_adamw and a data-parallel all-reduce read it as they always do
+ * The other buffer of each mode is only read. The additions run left to right, ((g0 + g1) + g2) + ..., one f32
+ * rounded add per element and micro-batch, without atomics: bitwise reproducible, NaN / inf propagate as an f32
+ * add propagates them. One streaming kernel (256 threads, 16-B loads and stores, grid-stride, scalar n % 4 tail);
+ * it moves 8 n bytes (FIRST) or 12 n bytes (ADD, LAST). Recorded into launch plans like any launch.
+ *   - grad and acc are 16-B aligned and must not overlap (an overlap of the two n-float ranges is rejected);
+ *   - any n >= 0; n == 0 returns MIT_OK without a launch;
+ *   - a NULL pointer, a mode outside 0..2, n < 0 and a misaligned pointer return MIT_ERR_INVALID (nothing launched).
+ * mit_grad_accumulate_blocks: the grid mit_grad_accumulate launches for n (0 for n <= 0; no launch): one trip of
+ * the grid-stride loop covers blocks * 256 * 4 floats. */
+enum { MIT_ACC_FIRST = 0, MIT_ACC_ADD = 1, MIT_ACC_LAST = 2 };
+long mit_grad_accumulate_blocks(long n);
+int mit_grad_accumulate(long n, float* grad, float* acc, int mode, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Batched greedy decoding with a KV cache (BASELINE config 5). Replaces the per-token full-prefix
  * recompute of ImageToTextModel.generate (model.py:171-242: decoder forward over ids[0..t], argmax

@@ -36,6 +36,7 @@ PROJECTION_DIM = 512
 
 # --- Training (reference config.py:76-100) ---
 BATCH_SIZE = 32
+GRAD_ACCUM_STEPS = 1  # batches per optimizer step (not in the reference: train.train_one_epoch's accum_steps)
 NUM_EPOCHS = 20
 LEARNING_RATE = 1e-4
 WEIGHT_DECAY = 1e-5

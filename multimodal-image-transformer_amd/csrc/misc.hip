@@ -1,5 +1,6 @@
 // Memory-bound kernels of the train step: encoder input assembly, decoder embedding, cross-entropy,
-// bias-gradient column sums, and the fused clip_grad_norm_ + AdamW optimizer step.
+// bias-gradient column sums, the fused clip_grad_norm_ + AdamW optimizer step, and the gradient
+// accumulation over micro-batches.
 #include "common.h"
 
 namespace {
@@ -505,6 +506,32 @@ __global__ __launch_bounds__(256) void adamw_kernel(long n, float* __restrict__ 
   }
 }
 
+// gradient accumulation over micro-batches: one f32 rounded add per element, no atomics, so the sum
+// ((g0 + g1) + g2) + ... is bitwise reproducible. FIRST: acc = grad (no zero-fill of acc is ever
+// needed); ADD: acc += grad; LAST: grad += acc (the total lands in the flat gradient buffer itself).
+constexpr int GA_BLOCKS = 4096;
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(long n, float* __restrict__ grad,
+                                                              float* __restrict__ acc) {
+  const long n4 = n / 4;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const f32x4 g = ((const f32x4*)grad)[i];
+    if (MODE == MIT_ACC_FIRST) {
+      ((f32x4*)acc)[i] = g;
+    } else {
+      const f32x4 a = ((const f32x4*)acc)[i];
+      const f32x4 s = f32x4{a[0] + g[0], a[1] + g[1], a[2] + g[2], a[3] + g[3]};
+      if (MODE == MIT_ACC_ADD) ((f32x4*)acc)[i] = s;
+      else ((f32x4*)grad)[i] = s;
+    }
+  }
+  for (long i = n4 * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    if (MODE == MIT_ACC_FIRST) acc[i] = grad[i];
+    else if (MODE == MIT_ACC_ADD) acc[i] = acc[i] + grad[i];
+    else grad[i] = acc[i] + grad[i];
+  }
+}
+
 template <typename T>
 __global__ void cast_kernel(long n, const float* __restrict__ src, T* __restrict__ dst) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
@@ -794,6 +821,30 @@ extern "C" int mit_adamw(long n, float* param, const float* grad, float* m, floa
     hipLaunchKernelGGL(adamw_kernel<false>, dim3(g), dim3(256), 0, s, n, param, grad, m, v, (bf16*)nullptr, norm_out,
                        lr, step, beta1, beta2, eps, weight_decay);
   MIT_LAUNCH_CHECK("mit_adamw");
+  return MIT_OK;
+}
+
+extern "C" long mit_grad_accumulate_blocks(long n) { return n <= 0 ? 0 : (long)grid_for(n / 4 + 1, 256, GA_BLOCKS); }
+
+extern "C" int mit_grad_accumulate(long n, float* grad, float* acc, int mode, void* stream) {
+  MIT_RECORD([=]() { return mit_grad_accumulate(n, grad, acc, mode, stream); });
+  MIT_CHECK_ARG(grad && acc, "mit_grad_accumulate: null pointer");
+  MIT_CHECK_ARG(mode == MIT_ACC_FIRST || mode == MIT_ACC_ADD || mode == MIT_ACC_LAST,
+                "mit_grad_accumulate: mode %d (MIT_ACC_FIRST 0, MIT_ACC_ADD 1, MIT_ACC_LAST 2)", mode);
+  MIT_CHECK_ARG(n >= 0, "mit_grad_accumulate: n = %ld", n);
+  MIT_CHECK_ARG(((uintptr_t)grad | (uintptr_t)acc) % 16 == 0, "mit_grad_accumulate: buffers must be 16-B aligned");
+  const uintptr_t g0 = (uintptr_t)grad, a0 = (uintptr_t)acc, bytes = (uintptr_t)n * sizeof(float);
+  MIT_CHECK_ARG(g0 + bytes <= a0 || a0 + bytes <= g0, "mit_grad_accumulate: grad and acc overlap");
+  if (n == 0) return MIT_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g((unsigned)mit_grad_accumulate_blocks(n));
+  if (mode == MIT_ACC_FIRST)
+    hipLaunchKernelGGL(grad_accumulate_kernel<MIT_ACC_FIRST>, g, dim3(256), 0, s, n, grad, acc);
+  else if (mode == MIT_ACC_ADD)
+    hipLaunchKernelGGL(grad_accumulate_kernel<MIT_ACC_ADD>, g, dim3(256), 0, s, n, grad, acc);
+  else
+    hipLaunchKernelGGL(grad_accumulate_kernel<MIT_ACC_LAST>, g, dim3(256), 0, s, n, grad, acc);
+  MIT_LAUNCH_CHECK("mit_grad_accumulate");
   return MIT_OK;
 }
 

@@ -13,7 +13,10 @@ build's DP stack:
     cfg1). Each bucket is all-reduced (SUM) asynchronously as soon as it is final; RCCL runs on
     its own stream, ordered after the producing kernels, overlapping the rest of the backward.
     ``finish_backward`` joins the buckets before clip + AdamW, which then run redundantly (and
-    identically) on every rank.
+    identically) on every rank;
+  * accumulated steps (model.train_step_accum): the count of ALL micro-batches is all-reduced once, the
+    micro-batches' backwards announce no buckets (none is final before the last accumulate), and
+    ``finish_accumulated`` all-reduces the whole flat gradient once after it, not overlapped.
 """
 from __future__ import annotations
 
@@ -85,6 +88,19 @@ class DataParallel:
 
     def finish_backward(self, loss: torch.Tensor):
         native.host_call(lambda: self._finish(loss))
+
+    # hooks called by model.train_step_accum -------------------------------------------------------
+    def finish_accumulated(self, loss: torch.Tensor):
+        """After the last micro-batch's MIT_ACC_LAST: the micro-batches ran without grads_ready (no bucket is
+        final before the last accumulate), so the whole flat gradient is all-reduced here, once per
+        accumulated step and not overlapped with any backward, then the loss. A host step of a recorded
+        program, like finish_backward."""
+        native.host_call(lambda: (self.all_reduce_grads(), dist.all_reduce(loss, group=self.group)))
+
+    def all_reduce_grads(self):
+        """SUM the whole flat gradient buffer over the ranks (one collective; the gaps between entries are
+        zero on every rank)."""
+        dist.all_reduce(self.store.grad, group=self.group)
 
     def _finish(self, loss: torch.Tensor):
         spans, self._covered = sorted(self._covered), []

@@ -134,6 +134,7 @@ class ImageToTextModel:
         self._prefetched = None
         self._slot_free = None           # native.HipEvents(2): end of the backward of the step that read slot i
         self._slot_freed = [False, False]  # slot i's event recorded since the slot was last read
+        self._step_terms = None          # train_step_accum: {count, loss sum, loss} of the accumulated step
         self._params: Optional["OrderedDict[str, torch.nn.Parameter]"] = None
         self._gen = 0  # bumped by every forward that writes the shared arenas (autograd staleness check)
 
@@ -365,9 +366,28 @@ class ImageToTextModel:
         gradient buffer. Returns the loss as a device scalar [1] (no host sync).
         next_images: the next batch's images, whose (frozen) encoder forward then runs on a second
         stream beside this step's decoder work (prefetch_encoder); results are unchanged."""
+        targets = target_tokens.to(self.device, torch.int64, non_blocking=True).contiguous()
+
+        def loss_terms(A):  # this step's own count, taken after the forward
+            native.zero(A.count_loss)
+            native.count_targets(targets, self.decoder_pad_idx, A.count)
+            if dist is not None:
+                dist.all_reduce_count(A.count)
+            return A.count, A.loss_sum
+        A = self._forward_backward(images, decoder_input_tokens, targets, loss_terms, next_images,
+                                   dist.grads_ready if dist is not None else None)
+        native.scalar_div(A.loss_sum, A.count, A.loss)
+        if dist is not None:
+            dist.finish_backward(A.loss)
+        return A.loss
+
+    def _forward_backward(self, images, decoder_input_tokens, targets, loss_terms, next_images, grads_ready):
+        """One batch's forward, CE and backward into the flat gradient buffer (the body train_step and every
+        micro-batch of train_step_accum share). loss_terms(A) -> (count, loss_sum), called between the
+        forward and the CE: the device scalars the CE divides its gradient by and adds its loss to.
+        Returns the activation arena."""
         images = images.to(self.device, non_blocking=True)
         tokens = decoder_input_tokens.to(self.device, torch.int64, non_blocking=True).contiguous()
-        targets = target_tokens.to(self.device, torch.int64, non_blocking=True).contiguous()
         B, T = tokens.shape
         mem, mem_ld, S, enc_rows, enc_ld = self._encode_memory(images, refresh=False)
         pf = self.prefetch_encoder_iter(next_images) if next_images is not None else None
@@ -385,25 +405,59 @@ class ImageToTextModel:
         A = dec.acts(B, T, S, True)
         native.step_inc(self.seed_t)
         logits, _ = dec.run_forward(tokens, mem, mem_ld, S, A, self.seed_t, True, tick=tick)
-        native.zero(A.count_loss)
-        native.count_targets(targets, self.decoder_pad_idx, A.count)
-        if dist is not None:
-            dist.all_reduce_count(A.count)
-        native.cross_entropy(logits, targets, self.decoder_pad_idx, A.count, A.loss_sum, True, row_loss=A.row_loss,
+        count, loss_sum = loss_terms(A)
+        native.cross_entropy(logits, targets, self.decoder_pad_idx, count, loss_sum, True, row_loss=A.row_loss,
                              V=dec.V, ld=dec.Vp)
         proj = (enc_rows, enc_ld, self.encoder_output_dim) if self.has_projection else None
         dec.run_backward(tokens, mem, mem_ld, S, A, self.seed_t, logits, proj_input=proj,
-                         grads_ready=dist.grads_ready if dist is not None else None, tick=tick)
+                         grads_ready=grads_ready, tick=tick)
         tick(1 << 30)
         if self._enc_stream is not None:  # this step's last reader of its encoder slot is issued
             if self._slot_free is None:
                 self._slot_free = native.HipEvents(2)
             self._slot_free.record_at(self._enc_slot, native.stream_ptr())
             self._slot_freed[self._enc_slot] = True
-        native.scalar_div(A.loss_sum, A.count, A.loss)
+        return A
+
+    def train_step_accum(self, micro_batches, dist=None, next_images: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One optimizer step's gradient over several micro-batches: a sequence of (images,
+        decoder_input_tokens, target_tokens) whose B and T may differ. Equal to train_step on their
+        concatenation: the non-PAD targets of ALL micro-batches are counted on the device before the first
+        forward (all-reduced once under ``dist``), every micro-batch's CE divides by that one count, and the
+        micro-batches' gradients are summed left to right into the flat gradient buffer (mit_grad_accumulate:
+        FIRST / ADD / LAST through store.accum, one rounded f32 add each, bitwise reproducible), where
+        optimizer.step, the DP all-reduce (once, after the last micro-batch: dist.finish_accumulated) and every
+        reader of store.grad find it. Each micro-batch advances the dropout seed once; the frozen encoder of
+        micro-batch i + 1 is prefetched beside micro-batch i, ``next_images`` (the next step's first
+        micro-batch) beside the last. Returns the global mean loss as a device scalar [1]; no host sync, no
+        torch kernel (recordable). One micro-batch is train_step itself, launch for launch."""
+        mbs = list(micro_batches)
+        if not mbs:
+            raise ValueError("train_step_accum: no micro-batch")
+        if len(mbs) == 1:
+            return self._train_step(*mbs[0], dist=dist, next_images=next_images)
+        pad = self.decoder_pad_idx
+        targets = [tg.to(self.device, torch.int64, non_blocking=True).contiguous() for _, _, tg in mbs]
+        if self._step_terms is None:  # {count, loss_sum, loss} of the step (an arena's own belong to one shape)
+            self._step_terms = torch.empty(3, dtype=torch.float32, device=self.device)
+        count, loss_sum, loss = self._step_terms[0:1], self._step_terms[1:2], self._step_terms[2:3]
+        native.zero(self._step_terms[0:2])
+        for tg in targets:
+            native.count_targets(tg, pad, count)
         if dist is not None:
-            dist.finish_backward(A.loss)
-        return A.loss
+            dist.all_reduce_count(count)
+        grad, acc = self.store.grad, self.store.ensure_accum()
+        last = len(mbs) - 1
+        for i, ((images, tokens, _), tg) in enumerate(zip(mbs, targets)):
+            # without grads_ready: no bucket is final before the last accumulate
+            self._forward_backward(images, tokens, tg, lambda A: (count, loss_sum),
+                                   mbs[i + 1][0] if i < last else next_images, None)
+            native.grad_accumulate(grad, acc, native.ACC_FIRST if i == 0 else native.ACC_LAST if i == last
+                                   else native.ACC_ADD)
+        native.scalar_div(loss_sum, count, loss)
+        if dist is not None:
+            dist.finish_accumulated(loss)
+        return loss
 
     def make_graphed_step(self, optimizer, images, decoder_input_tokens, target_tokens, max_norm: float):
         """Capture train_step + optimizer.step(max_norm) (train.py:75-100, ~300 kernel launches) into

@@ -156,6 +156,8 @@ SIGNATURES = {
     "mit_step_inc": (I, [vp, vp]),
     "mit_stamp": (I, [vp, I, vp]),
     "mit_adamw": (I, [L, vp, vp, vp, vp, vp, vp, vp, vp, Fl, Fl, Fl, Fl, vp]),
+    "mit_grad_accumulate_blocks": (L, [L]),
+    "mit_grad_accumulate": (I, [L, vp, vp, I, vp]),
     "mit_cast_f32": (I, [I, L, vp, vp, vp]),
     "mit_zero": (I, [vp, L, vp]),
     "mit_scalar_div": (I, [vp, vp, vp, vp]),
@@ -829,6 +831,19 @@ def step_inc(step):
 def adamw(param, grad, m, v, shadow, norm_out, lr, step, beta1, beta2, eps, weight_decay, n=None):
     _check(lib().mit_adamw(param.numel() if n is None else n, ptr(param), ptr(grad), ptr(m), ptr(v), ptr(shadow), ptr(norm_out), ptr(lr),
                            ptr(step), beta1, beta2, eps, weight_decay, stream_ptr()), "mit_adamw")
+
+
+ACC_FIRST, ACC_ADD, ACC_LAST = 0, 1, 2  # mit_grad_accumulate modes (include/mit_hip.h)
+
+
+def grad_accumulate_blocks(n):
+    return lib().mit_grad_accumulate_blocks(n)
+
+
+def grad_accumulate(grad, acc, mode, n=None):
+    """FIRST: acc = grad; ADD: acc += grad; LAST: grad += acc (flat f32 buffers, one rounded add per element)."""
+    _check(lib().mit_grad_accumulate(grad.numel() if n is None else n, ptr(grad), ptr(acc), mode, stream_ptr()),
+           "mit_grad_accumulate")
 
 
 def cast_f32(src, dst, n=None):

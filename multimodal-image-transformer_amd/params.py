@@ -38,6 +38,7 @@ class FlatParams:
             self.shadow = torch.zeros(self.numel, dtype=compute_dtype, device=device)
         self.exp_avg = None
         self.exp_avg_sq = None
+        self.accum = None  # ensure_accum(): allocated by the first step over more than one micro-batch
         self._synced = self.master._version
 
     # views (cached: the buffers are allocated once and only ever updated in place) -------------
@@ -90,6 +91,13 @@ class FlatParams:
 
     def zero_grad(self):
         native.zero(self.grad)
+
+    def ensure_accum(self):
+        """The gradient accumulator of a step over several micro-batches (model.train_step_accum): numel f32
+        laid out like ``grad``. Left uninitialised: the first micro-batch overwrites it (MIT_ACC_FIRST)."""
+        if self.accum is None:
+            self.accum = torch.empty(self.numel, dtype=torch.float32, device=self.device)
+        return self.accum
 
     def ensure_optimizer_state(self):
         if self.exp_avg is None:

@@ -10,6 +10,8 @@ per batch zero_grad -> forward -> criterion -> backward -> clip_grad_norm_(grad_
   * any other optimizer / criterion (torch.optim.AdamW(model.parameters()), label smoothing, ...):
     the reference's own call sequence through autograd (model.forward's backward is the HIP
     backward).
+``train_one_epoch(..., accum_steps=k)`` (fused path) takes the batches k at a time as the micro-batches of one
+optimizer step (model.train_step_accum): the step at their concatenation.
 ``main()`` runs the loop on synthetic batches (the dataset / tokenizer / W&B / Hub plumbing of the
 reference main() is out of scope: SURVEY.md §2a) and writes reference-format checkpoints.
 """
@@ -54,8 +56,75 @@ def _staged(model, dataloader):
         yield b
 
 
+def micro_groups(iterable, k: int):
+    """Consecutive items k at a time, as lists; a shorter last group when the items run out."""
+    if k < 1:
+        raise ValueError(f"micro_groups: k = {k} (at least 1)")
+
+    def groups():
+        group = []
+        for item in iterable:
+            group.append(item)
+            if len(group) == k:
+                yield group
+                group = []
+        if group:
+            yield group
+    return groups()
+
+
+def optimizer_steps(batches: int, accum_steps: int, epochs: int) -> int:
+    """Optimizer (and scheduler) steps of a run: one per group of accum_steps batches, the last group
+    of an epoch possibly shorter."""
+    if accum_steps < 1:
+        raise ValueError(f"accum_steps = {accum_steps} (at least 1)")
+    return -(-batches // accum_steps) * epochs
+
+
+def _train_epoch_accum(model, dataloader, optimizer, grad_clip_value, scheduler, epoch, log_interval, wandb_run, dist,
+                       accum_steps):
+    """train_one_epoch over groups of accum_steps batches: each group is one model.train_step_accum, one
+    optimizer.step, one scheduler.step and one loss; the average and the log lines are per optimizer step."""
+    total = torch.zeros(1, dtype=torch.float32, device=model.device)
+    first_bad = torch.full((1,), -1, dtype=torch.int64, device=model.device)
+    try:
+        steps_per_epoch = -(-len(dataloader) // accum_steps)
+    except TypeError:
+        steps_per_epoch = 1
+    n = 0
+    it = micro_groups(_staged(model, dataloader), accum_steps)
+    group = next(it, None)
+    i = -1
+    while group is not None:
+        i += 1
+        nxt = next(it, None)
+        optimizer.zero_grad()
+        # the frozen encoder of the next group's first micro-batch runs beside this group's last one
+        loss = model.train_step_accum([(b["images"], b["decoder_input_tokens"], b["target_tokens"]) for b in group],
+                                      dist=dist, next_images=nxt[0]["images"] if nxt is not None else None)
+        optimizer.step(grad_clip_value if grad_clip_value > 0 else 0.0)
+        if scheduler:
+            scheduler.step()
+        total += loss
+        bad = ~torch.isfinite(loss)
+        first_bad.copy_(torch.where(bad & (first_bad < 0), torch.full_like(first_bad, i), first_bad))
+        n += 1
+        if log_interval and (i + 1) % log_interval == 0:
+            if dist is None:
+                _check_finite(first_bad, epoch)
+            lv = loss.item()
+            print(f"epoch {epoch + 1} step {i + 1} ({len(group)} micro-batches): loss {lv:.4f} "
+                  f"lr {_lr_of(optimizer):.2e}", flush=True)
+            if wandb_run:
+                wandb_run.log({"train_batch_loss": lv, "learning_rate": _lr_of(optimizer),
+                               "global_step": epoch * max(1, steps_per_epoch) + i + 1})
+        group = nxt
+    _check_finite(first_bad, epoch)
+    return (total / max(n, 1)).item()
+
+
 def train_one_epoch(model, dataloader, optimizer, criterion, device, grad_clip_value, scheduler, epoch,
-                    log_interval, wandb_run, dist=None):
+                    log_interval, wandb_run, dist=None, accum_steps=1):
     """train.py:62-123. Returns the average training loss of the epoch.
 
     With the fused optimizer (optim.AdamW) and the reference criterion, each batch is ONE kernel
@@ -63,11 +132,23 @@ def train_one_epoch(model, dataloader, optimizer, criterion, device, grad_clip_v
     With any other optimizer (e.g. torch.optim.AdamW over model.parameters()) or criterion, the
     reference's own call sequence runs (train.py:80-100): zero_grad, logits = model(...),
     loss = criterion(...), loss.backward() (the HIP backward via autograd), clip_grad_norm_,
-    optimizer.step()."""
+    optimizer.step().
+
+    accum_steps = k > 1 (fused path only): consecutive batches are grouped k at a time (micro_groups; a
+    shorter last group is one smaller step) and each group is ONE optimizer step over the summed gradients
+    (model.train_step_accum), equal to the step at the concatenated batch; the returned average and the log
+    lines are then per optimizer step."""
+    if accum_steps < 1:
+        raise ValueError(f"accum_steps = {accum_steps} (at least 1)")
     model.train()
     fused = isinstance(optimizer, optim.AdamW) and _fused_loss_ok(model, criterion)
     if dist is not None and not fused:
         raise ValueError("data-parallel training runs the fused step: pass optim.AdamW and the reference criterion")
+    if accum_steps > 1:
+        if not fused:
+            raise ValueError("gradient accumulation runs the fused step: pass optim.AdamW and the reference criterion")
+        return _train_epoch_accum(model, dataloader, optimizer, grad_clip_value, scheduler, epoch, log_interval,
+                                  wandb_run, dist, accum_steps)
     total = torch.zeros(1, dtype=torch.float32, device=model.device)
     # failure detection (SURVEY.md §5): the index of the first batch whose loss is NaN / inf, tracked on the
     # device (no per-step sync; the reference's all-PAD rows give NaN, dataset.py:116-130). Checked at the end
@@ -365,23 +446,33 @@ def shard_batches(batches, rank: int, world: int):
         yield {k: v[lo:hi] for k, v in b.items()}
 
 
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="Train the captioning model on synthetic batches (MI355X path)")
+    ap.add_argument("--epochs", type=int, default=1)
+    ap.add_argument("--batches", type=int, default=20)
+    ap.add_argument("--batch-size", type=int, default=config.BATCH_SIZE,
+                    help="global batch (all ranks) of ONE micro-batch")
+    ap.add_argument("--accum-steps", type=int, default=config.GRAD_ACCUM_STEPS,
+                    help="batches per optimizer step (gradient accumulation; 1 = step after every batch)")
+    ap.add_argument("--seq-len", type=int, default=64)
+    ap.add_argument("--out", default=None, help="checkpoint prefix (optional)")
+    ap.add_argument("--resume", default=getattr(config, "RESUME_CHECKPOINT_PATH", None),
+                    help="resume from a .pt checkpoint (train.py:343-375)")
+    return ap
+
+
 def main(argv=None):
-    """train.py:282-452 on synthetic batches. Data parallel when launched with WORLD_SIZE > 1
+    """train.py:282-452 on synthetic batches. --accum-steps k groups k consecutive batches into one
+    optimizer step (train_one_epoch's accum_steps); the warm-up schedule then counts optimizer steps. Data parallel when launched with WORLD_SIZE > 1
     (torchrun, one process per GPU; RCCL): every rank takes its slice of each global batch of
     --batch-size pairs (shard_batches), the decoder gradients are all-reduced by bucket during the
     backward (dist.DataParallel) with the loss normalised by the GLOBAL non-PAD count, so the step
     equals the single-process step at the global batch; validation runs the whole batch on every
     rank (identical results), and only rank 0 writes checkpoints. Returns the per-epoch
     (train, val) losses."""
-    ap = argparse.ArgumentParser(description="Train the captioning model on synthetic batches (MI355X path)")
-    ap.add_argument("--epochs", type=int, default=1)
-    ap.add_argument("--batches", type=int, default=20)
-    ap.add_argument("--batch-size", type=int, default=config.BATCH_SIZE, help="global batch (all ranks)")
-    ap.add_argument("--seq-len", type=int, default=64)
-    ap.add_argument("--out", default=None, help="checkpoint prefix (optional)")
-    ap.add_argument("--resume", default=getattr(config, "RESUME_CHECKPOINT_PATH", None),
-                    help="resume from a .pt checkpoint (train.py:343-375)")
-    args = ap.parse_args(argv)
+    args = build_parser().parse_args(argv)
+    if args.accum_steps < 1:
+        raise ValueError(f"--accum-steps {args.accum_steps} (at least 1)")
     from dist import DataParallel, init_from_env
     rank, world = init_from_env()
     torch.manual_seed(config.RANDOM_SEED)
@@ -391,7 +482,7 @@ def main(argv=None):
                       eps=config.ADAM_EPS, weight_decay=config.WEIGHT_DECAY)
     sched = None
     if config.WARMUP_STEPS > 0:
-        sched = LinearWarmup(opt, config.WARMUP_STEPS, args.batches * args.epochs)
+        sched = LinearWarmup(opt, config.WARMUP_STEPS, optimizer_steps(args.batches, args.accum_steps, args.epochs))
     train = synthetic_loader(args.batches, args.batch_size, args.seq_len, config.VOCAB_SIZE, model.encoder.image, 1)
     val = synthetic_loader(2, args.batch_size, args.seq_len, config.VOCAB_SIZE, model.encoder.image, 2)
     start, best = load_checkpoint(model, opt, sched, args.resume)
@@ -404,7 +495,7 @@ def main(argv=None):
     for epoch in range(start, args.epochs):
         t0 = time.time()
         tl = train_one_epoch(model, train, opt, None, "cuda", config.GRAD_CLIP_VALUE, sched, epoch,
-                             config.LOG_INTERVAL if rank == 0 else 0, None, dist=dp)
+                             config.LOG_INTERVAL if rank == 0 else 0, None, dist=dp, accum_steps=args.accum_steps)
         vl = evaluate(model, val, None, "cuda")
         if world > 1:
             # every rank takes rank 0's validation loss, so the best-checkpoint decision (and the barrier
